@@ -14,9 +14,15 @@ D=128) at bs=256 / ctx=4096 / page_size=16 with shuffled pages: per layer
 With N GPUs the path is tensor-parallel (Hq/N, max(1,Hkv/N) heads per rank; same page table on
 every rank), total work fixed => "scaling": "strong".  value = bs / step time (decode tokens/s).
 
-Also reported on the same JSON line:
+A plain run sets the step up, warms up, times the K steps and prints the result line (metric, value, ms_per_step, the
+decode kernel's roofline from the events inside the timed steps).  `--dump-outputs DIR` also writes what the last timed
+step computed as DIR/<name>.npy (see dump_outputs).
+
+Reported on the same JSON line by every run:
   roofline      -- decode attention kernel: algorithmic KV+Q+O bytes per launch / average launch
-                   duration measured with HIP events inside the timed region, vs 8 TB/s.
+                   duration measured with HIP events inside the timed region, vs 8 TB/s
+                   (roofline.back_to_back, launches of their own after the timed steps, needs --full).
+and with --full only (legs that take runs of their own):
   cpu_baseline  -- (N=1, rank 0) the same decode on the host cores: the reference's own compiled
                    C++ CPU kernel (oracle/_ref, kind "reference") when it loads and runs here, else
                    the C restatement (oracle/rx_oracle.c, kind "port"); one layer, bounded sample.
@@ -53,6 +59,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--settle", type=int, default=5, help="untimed steps run before the warmup steps (state bring-up)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary leg: extend, radix-hit / verify / MLA / heterogeneous "
+                         "decode, the `extra` child runs, the CPU baselines and the parity figure, the back-to-back and host-enqueue "
+                         "figures, and (N > 1) the all-reduce figures; the --no-* switches below drop single legs of a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (per layer: attention output and o_proj "
+                         "output) as DIR/<name>.npy in float32; inputs are seeded, so two runs with the same arguments compare "
+                         "output for output")
     ap.add_argument("--bs", type=int, default=256)
     ap.add_argument("--ctx", type=int, default=4096)
     ap.add_argument("--layers", type=int, default=32)
@@ -230,6 +244,7 @@ def make_decode_state(args, tp, dev, shared_prefix=0, cascade=False):
     del w_full
     st.slots = slots
     st.overlap, st.ev_stride = True, 1
+    st.kept = None  # --dump-outputs: {layer: (attention output, o_proj output)} of the latest step
     return st
 
 
@@ -262,6 +277,8 @@ def decode_layers(st, fb, world, lo, hi, ev_pairs=None, attn_only_first=False, s
         if pending is not None:
             pending.wait()
         pending = st.o_proj.forward(o, overlap=world > 1 and st.overlap)
+        if st.kept is not None:  # (a captured segment keeps its tensors alive: every replay refills them)
+            st.kept[li] = (o, pending.tensor)
     if pending is not None:
         pending.wait()
 
@@ -987,7 +1004,7 @@ def child_decode_leg(args, argv, timeout=900):
     from scratch, this process holds no pool meanwhile) -- returns the fields of its JSON line that matter."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extend", "--no-radix-hit", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extend", "--no-radix-hit", "--no-cpu-baseline",
            "--no-extra", "--full-json", "--steps", "10", "--warmup", "3", "--layers", str(args.layers), "--kv-layout",
            args.kv_layout] + argv
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
@@ -1682,7 +1699,7 @@ def _r(x, n=4):
 
 
 def compact_record(out):
-    """The FINAL line of a default run: the contract's keys plus, inside `roofline` (the dict the driver keeps), the
+    """The FINAL line of a run (the legs named below are those of a `--full` run): the contract's keys plus, inside `roofline` (the dict the driver keeps), the
     extend half of the metric and one number per other measured leg.  Everything else stays in the full record
     ('[bench-full] ' line / gpurun_out/bench_full.json).  Kept under 2 KB (the 15-KB line pushed
     `extend` out of the driver's 8-KB tail)."""
@@ -1843,6 +1860,30 @@ def emit(out, args):
     print(line, flush=True)
 
 
+def dump_outputs(path, kept, budget=48 << 20):
+    """--dump-outputs: what the last timed step handed to its caller, as float32 .npy files -- per layer the decode
+    attention output [bs, Hq * D] and the o_proj output [bs, hidden] (N > 1: rank 0's head shard of the attention output, the
+    o_proj output after the all-reduce).  The last layer is written in full; of every layer, the same fixed sample of
+    requests (seeded, sorted) -- both sized so that the files stay under `budget` bytes together."""
+    os.makedirs(path, exist_ok=True)
+    layers = sorted(kept)
+    attn = [kept[l][0].reshape(kept[l][0].shape[0], -1) for l in layers]
+    proj = [kept[l][1].reshape(kept[l][1].shape[0], -1) for l in layers]
+    bs = attn[0].shape[0]
+    row_bytes = 4 * (attn[0].shape[1] + proj[0].shape[1])
+
+    def pick(n):
+        rows = np.sort(np.random.default_rng(0).choice(bs, size=min(bs, max(1, n)), replace=False))
+        return torch.from_numpy(rows).to(attn[0].device)
+
+    last, rows = pick(budget // 2 // row_bytes), pick(budget // 2 // (row_bytes * len(layers)))
+    out = {"attn_out_last_layer": attn[-1][last], "o_proj_out_last_layer": proj[-1][last],
+           "attn_out_all_layers_sample": torch.stack([a[rows] for a in attn]),
+           "o_proj_out_all_layers_sample": torch.stack([p[rows] for p in proj])}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     if args.cpu_worker:
@@ -1871,6 +1912,8 @@ def main():
         os.environ["RX_CUSTOM_AR"] = "1"
     st = make_decode_state(args, tp, dev)
     st.overlap = True
+    if args.dump_outputs and not args.ar_leg:
+        st.kept = {}
     fb = ForwardBatch.for_decode(st.req_pool_indices, st.seq_lens, st.out_cache_loc, st.seq_lens_cpu)
     comm_backend = os.environ.get("RX_BENCH_BACKEND", "nccl") if world > 1 else "none"
     contact = None
@@ -1936,12 +1979,16 @@ def main():
     timed["on"] = True
     dt = time_steps(step, args.steps, 0, world)
     timed["on"] = False
+    if st.kept is not None and rank == 0:
+        dump_outputs(args.dump_outputs, st.kept)
     # host enqueue time of one step (GPU idle at start, no sync inside): launch-path overhead
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    step()
-    host_enqueue_ms = (time.perf_counter() - t0) * 1e3
-    torch.cuda.synchronize()
+    host_enqueue_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        host_enqueue_ms = (time.perf_counter() - t0) * 1e3
+        torch.cuda.synchronize()
     ms_per_step = dt / args.steps * 1e3
     value = args.bs / (dt / args.steps)
 
@@ -1982,7 +2029,7 @@ def main():
                 "launch_ms_min": float(durs.min()), "launch_ms_median": float(np.median(durs)),
                 "launch_ms_max": float(durs.max())}
     # the same launch back to back inside one captured graph (after the timed region; see GraphStep.probe_back_to_back)
-    if graph_step_box[0] is not None and world == 1 and not no_events:
+    if args.full and graph_step_box[0] is not None and world == 1 and not no_events:
         try:
             b2b_ms, b2b_n = graph_step_box[0].probe_back_to_back()
             b2b = bytes_per_launch / (b2b_ms * 1e-3) / 1e9
@@ -1999,6 +2046,7 @@ def main():
         allf = [torch.zeros_like(fr) for _ in range(world)]
         dist.all_gather(allf, fr)
         roofline["per_rank_frac"] = [float(x.item()) for x in allf]
+    if world > 1 and args.full:
         try:
             ar = allreduce_figures(st, fb, world, args, make_step)
         except Exception as e:  # noqa: BLE001
@@ -2046,7 +2094,7 @@ def main():
     if args.tp_sim:
         out["config"]["tp_sim"] = ("ONE rank's shard of a TP=%d job on one GPU, no collective: not a %d-GPU number"
                                    % (tp, tp))
-    if rank == 0 and world == 1 and not args.no_extend:
+    if rank == 0 and world == 1 and args.full and not args.no_extend:
         try:
             out["extend"] = extend_bench(args, dev, world)
         except Exception as e:
@@ -2063,7 +2111,7 @@ def main():
                 except Exception as e:  # noqa: BLE001
                     out["extend"][key] = {"error": f"{type(e).__name__}: {e}"}
                     torch.cuda.empty_cache()
-    if world > 1 and not args.no_extend:
+    if world > 1 and args.full and not args.no_extend:
         # the extend half of the metric at N GPUs: every rank runs ITS head shard of the same config-3 chunk (heads are
         # independent: no exchange inside attention); whole-job TFLOP/s = all ranks' FLOPs / the slowest rank's time
         import torch.distributed as dist
@@ -2084,7 +2132,7 @@ def main():
             out["extend"] = ext
         except Exception as e:  # noqa: BLE001
             out["extend"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_radix_hit:
+    if rank == 0 and world == 1 and args.full and not args.no_radix_hit:
         try:
             del st, fb, step
             ev_pairs.clear()
@@ -2104,7 +2152,7 @@ def main():
             out["heterogeneous_decode"] = hetero_decode_bench(dev)
         except Exception as e:
             out["heterogeneous_decode"] = {"error": str(e)}
-    if rank == 0 and world == 1 and not args.no_extra and not args.tp_sim:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not args.tp_sim:
         st = fb = step = None  # (the radix-hit branch above may have dropped them already)
         ev_pairs.clear()
         import gc
@@ -2114,7 +2162,7 @@ def main():
             out["extra"] = extra_legs(args, dev)
         except Exception as e:  # noqa: BLE001
             out["extra"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
         if out["cpu_baseline"].get("kind") == "reference" and not args.tp_sim and (args.bs, args.ctx) == (256, 4096):
             try:

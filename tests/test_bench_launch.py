@@ -66,7 +66,7 @@ def test_bench_gpus_2_runs_two_ranks_on_one_gpu(extra):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--settle", "1", "--bs", "16", "--ctx", "512", "--layers", "4", "--no-cpu-baseline", "--full-json"] + extra,
+                        "--settle", "1", "--bs", "16", "--ctx", "512", "--layers", "4", "--full", "--no-cpu-baseline", "--full-json"] + extra,
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -100,7 +100,7 @@ def test_bench_gpus_8_first_contact_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--settle", "1", "--bs", "16", "--ctx", "512", "--layers", "2", "--no-cpu-baseline", "--full-json",
+                        "--settle", "1", "--bs", "16", "--ctx", "512", "--layers", "2", "--full", "--no-cpu-baseline", "--full-json",
                         "--no-custom-ar-leg"],   # (the two-shot kernel at world 8: tests/test_gpu_allreduce.py; a second 8-rank job here costs minutes)
                        capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -118,16 +118,28 @@ def test_bench_gpus_8_first_contact_on_one_gpu():
 
 
 @pytest.mark.gpu
-def test_bench_tp_sim_shard_replays_from_hip_graphs():
+def test_bench_tp_sim_shard_replays_from_hip_graphs(tmp_path):
     """One rank's shard of a TP=8 job (no collective) under graph replay: the step is launched as HIP-graph replays
     and the roofline kernel is still timed live."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tp-sim", "8", "--steps", "3", "--warmup", "1",
-                        "--settle", "1", "--bs", "64", "--ctx", "1024", "--layers", "8", "--no-cpu-baseline",
-                        "--no-extend", "--no-radix-hit", "--no-extra"], capture_output=True, text=True, timeout=900)
+                        "--settle", "1", "--bs", "64", "--ctx", "1024", "--layers", "8", "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    # --dump-outputs: the replayed step's per-layer outputs (4 q heads x 128, hidden 4096), finite and not all zero
+    import numpy as np
+
+    dumped = {n: np.load(tmp_path / "dump" / n) for n in os.listdir(tmp_path / "dump")}
+    assert {n: a.shape for n, a in dumped.items()} == {
+        "attn_out_last_layer.npy": (64, 512), "o_proj_out_last_layer.npy": (64, 4096),
+        "attn_out_all_layers_sample.npy": (8, 64, 512), "o_proj_out_all_layers_sample.npy": (8, 64, 4096)}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0 for a in dumped.values())
+    assert np.array_equal(dumped["attn_out_all_layers_sample.npy"][-1], dumped["attn_out_last_layer.npy"])
     # default output: the full record on a '[bench-full] ' line, then ONE compact JSON line, last
     lines = r.stdout.splitlines()
     full = json.loads(next(ln for ln in lines if ln.startswith("[bench-full] "))[len("[bench-full] "):])
+    # a plain run (no --full) times its steps and nothing else: no secondary leg in the record
+    assert not {"extend", "radix_hit_decode", "spec_verify", "mla_decode", "heterogeneous_decode", "extra", "cpu_baseline"} & set(full)
+    assert "back_to_back" not in full["roofline"] and full["config"]["host_enqueue_ms_per_step"] is None and full["steps"] == 3
     assert full["n_gpus"] == 1 and full["config"]["step_launch"].startswith("hip-graph")
     assert full["roofline"]["launches"] == 3 and full["roofline"]["avg_launch_ms"] > 0
     assert lines[-1].startswith("{") and len(lines[-1]) < 2660
@@ -137,7 +149,7 @@ def test_bench_tp_sim_shard_replays_from_hip_graphs():
 
 
 def test_compact_line_carries_both_halves_of_the_metric():
-    """The final line of a default run: under 2.6 KB, the contract's keys, and -- as SCALAR keys of the
+    """The final line of a `--full` run: under 2.6 KB, the contract's keys, and -- as SCALAR keys of the
     `roofline` dict, right after `frac` / `traffic`, at most 24 keys in all (the driver's parser keeps scalars only and cut the
     tail in round 5) -- the extend half of the metric plus the legs the verdict sets targets on.  Fed with a committed full record."""
     bench = _load_bench()
@@ -183,3 +195,38 @@ def test_compact_line_carries_both_halves_of_the_metric():
         bench.emit(broken, A)
     last = json.loads(buf.getvalue().splitlines()[-1])
     assert last["value"] == full["value"] and "compact_record_error" in last and last["roofline"]["frac"] == full["roofline"]["frac"]
+
+
+def test_dump_outputs_files_dtype_seeded_rows_and_budget(tmp_path):
+    """--dump-outputs: four float32 .npy files -- the last layer in full while it fits half the budget, of every layer the
+    same seeded, sorted sample of requests -- within the byte budget, values unchanged, the same choice on every call."""
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    L, bs, hq, d, hid = 3, 40, 4, 16, 96
+    g = torch.Generator().manual_seed(0)
+    kept = {l: (torch.randn(bs, hq, d, generator=g).to(torch.bfloat16), torch.randn(bs, hid, generator=g).to(torch.bfloat16))
+            for l in range(L)}
+    row_bytes = 4 * (hq * d + hid)
+    budget = 2 * 10 * L * row_bytes          # room for 10 requests of every layer, and for 30 of the last one
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), kept, budget=budget)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["attn_out_all_layers_sample.npy", "attn_out_last_layer.npy", "o_proj_out_all_layers_sample.npy",
+                     "o_proj_out_last_layer.npy"]
+    arr = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in arr.values())
+    assert sum(a.nbytes for a in arr.values()) <= budget
+    rows = np.sort(np.random.default_rng(0).choice(bs, size=10, replace=False))
+    last = np.sort(np.random.default_rng(0).choice(bs, size=30, replace=False))
+    attn = [kept[l][0].reshape(bs, -1).float().numpy() for l in range(L)]
+    proj = [kept[l][1].float().numpy() for l in range(L)]
+    assert np.array_equal(arr["attn_out_all_layers_sample"], np.stack([a[rows] for a in attn]))
+    assert np.array_equal(arr["o_proj_out_all_layers_sample"], np.stack([p[rows] for p in proj]))
+    assert np.array_equal(arr["attn_out_last_layer"], attn[-1][last]) and np.array_equal(arr["o_proj_out_last_layer"], proj[-1][last])
+    for n in names:
+        assert np.array_equal(arr[n[:-4]], np.load(tmp_path / "b" / n))
+    # with room for it, the last layer is written in full
+    bench.dump_outputs(str(tmp_path / "c"), kept, budget=1 << 20)
+    assert np.array_equal(np.load(tmp_path / "c" / "o_proj_out_last_layer.npy"), proj[-1])

@@ -19,9 +19,9 @@ if full:
     open(sys.argv[2] + "_full.json", "w").write(full[-1] + "\n")
 PY
 }
-python3 $R/bench.py > $OUT/bench_default.out 2> $OUT/bench_default.err
+python3 $R/bench.py --full > $OUT/bench_default.out 2> $OUT/bench_default.err
 split_lines $OUT/bench_default.out $OUT/${TAG}_bench_default
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $R/bench.py --no-extra --no-cpu-baseline --no-radix-hit --no-peaked --steps 2 --warmup 1 > $OUT/bench_kt.out 2> $OUT/kt.err
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $R/bench.py --full --no-extra --no-cpu-baseline --no-radix-hit --no-peaked --steps 2 --warmup 1 > $OUT/bench_kt.out 2> $OUT/kt.err
 split_lines $OUT/bench_kt.out $OUT/${TAG}_bench_under_kernel_trace
 # counter passes: eager launches (--no-graph), one counter family per pass, nothing but --pmc on the command line
 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pf --output-format csv -- python3 $R/bench.py --no-extra --no-graph --no-cpu-baseline --no-extend --no-radix-hit --steps 2 --warmup 1 > /dev/null 2> $OUT/pf.err
@@ -32,10 +32,10 @@ PS=64 FP8=1 rocprofv3 --pmc FETCH_SIZE -d $OUT/mla8_pmc -o p --output-format csv
 python3 $R/profiles/summarize.py $OUT $TAG
 # SHORT decode launches (round 6): the shard legs' kernel under the kernel trace -- rocprofv3's duration of the decode kernel
 # is what bench.py's back-to-back figure (GraphStep.probe_back_to_back) must agree with, not the single launch between events
-rocprofv3 --kernel-trace --stats -d $OUT/c3 -o c3 --output-format csv -- python3 $R/bench.py --model llama3-70b --tp-sim 8 --bs 128 --ctx 4096 --layers 80 --no-extend --no-radix-hit --no-cpu-baseline --no-extra --steps 3 --warmup 1 > $OUT/c3.out 2> $OUT/c3.err
+rocprofv3 --kernel-trace --stats -d $OUT/c3 -o c3 --output-format csv -- python3 $R/bench.py --full --model llama3-70b --tp-sim 8 --bs 128 --ctx 4096 --layers 80 --no-extend --no-radix-hit --no-cpu-baseline --no-extra --steps 3 --warmup 1 > $OUT/c3.out 2> $OUT/c3.err
 split_lines $OUT/c3.out $OUT/${TAG}_config3_shard_under_kernel_trace
 cp $(find $OUT/c3 -name "*_kernel_stats.csv" | head -1) $R/profiles/${TAG}_config3_shard_kernel_stats.csv 2>/dev/null
-rocprofv3 --kernel-trace --stats -d $OUT/tp8 -o tp8 --output-format csv -- python3 $R/bench.py --tp-sim 8 --no-extend --no-radix-hit --no-cpu-baseline --no-extra --steps 3 --warmup 1 > $OUT/tp8.out 2> $OUT/tp8.err
+rocprofv3 --kernel-trace --stats -d $OUT/tp8 -o tp8 --output-format csv -- python3 $R/bench.py --full --tp-sim 8 --no-extend --no-radix-hit --no-cpu-baseline --no-extra --steps 3 --warmup 1 > $OUT/tp8.out 2> $OUT/tp8.err
 split_lines $OUT/tp8.out $OUT/${TAG}_tp8_shard_under_kernel_trace
 cp $(find $OUT/tp8 -name "*_kernel_stats.csv" | head -1) $R/profiles/${TAG}_tp8_shard_kernel_stats.csv 2>/dev/null
 cp $OUT/${TAG}_config3_shard_under_kernel_trace_full.json $OUT/${TAG}_tp8_shard_under_kernel_trace_full.json $R/profiles/ 2>/dev/null
