@@ -440,6 +440,62 @@ int rx_decode_units(const int32_t* req_to_token, int64_t req_row_stride, const v
                     int max_kv_splits, const int32_t* split_items, const int32_t* split_items_count, int cap,
                     const int32_t* request_order, int bs, int32_t* unit_desc, int32_t* unit_first_slots, void* stream);
 
+/* ---- 4-bit KV pool (MXFP4, blocks of 16) ----------------------------------------------------------
+ * MHATokenToKVPoolFP4 (srt/mem_cache/memory_pool.py:2959-3110, --kv-cache-dtype fp4_e2m1) in the format of
+ * FP4MXBlock16KVQuantizeUtil (srt/layers/quantization/kvfp4_tensor.py:56-147): 0.5625 B per element.
+ *
+ * Packing.  A (slot, kv head) row of D elements is D/2 data bytes -- element 2i in the low nibble of byte i, element
+ * 2i+1 in the high nibble -- and D/16 scale bytes in the same order, one per block of 16 elements.
+ * Decoding.  value = E2M1[nibble & 7] * (-1)^(nibble >> 3) * 2^(scale - 127), E2M1 = 0, .5, 1, 1.5, 2, 3, 4, 6.
+ * Quantising = the reference's batched_quantize EVALUATED IN FP32 (what its compiled form computes from 16-bit inputs;
+ * its eager evaluation in bf16 rounds log2 to bf16 and differs in ~1.3 % of the blocks -- the contract is fp32):
+ *   e = max(-33, ceil(log2(block_max / 6))), the smallest integer with 6 * 2^e >= block_max (an all-zero block: scale
+ *   byte 94); s = x / 2^e; magnitude code = the number of bounds {.25, .75, 1.25, 1.75, 2.5, 3.5, 5} that are <= |s| --
+ *   ties go UP in magnitude, this is not round-to-nearest-even -- and the sign bit is s < 0.  With k_scale / v_scale
+ *   != 1 the input is first divided and rounded to its own 16-bit dtype (the reference's in-place div_, as
+ *   rx_store_kv_fp8).
+ * Dequantised values are exact in bf16, and in fp16 while they are normal fp16 numbers (the quantiser fed fp16 inputs
+ * never produces a value above 65504).  Blocks whose non-zero values fall below the call dtype's normal range, and the
+ * scale bytes 0 and 255, are outside the contract.
+ * Layouts.  NHD, the reference's: data [slots, Hkv, D/2], scales [slots, Hkv * D/16].  HND pages: data [pages, Hkv,
+ * page, D/2], scales [pages, Hkv, page, D/16].  The data buffers ride in rx_kv_layout as BYTE buffers with BYTE strides
+ * (kv_fp8 is ignored by the entry points below); the scale buffers and their byte strides -- same addressing formula --
+ * ride in rx_kv_mx4_scales beside it. */
+typedef struct rx_kv_mx4_scales {
+  const void* k_scale_buf;
+  const void* v_scale_buf;
+  int64_t k_page_stride, k_tok_stride, k_head_stride;
+  int64_t v_page_stride, v_tok_stride, v_head_stride;
+} rx_kv_mx4_scales;
+
+/* The quantising store (MHATokenToKVPoolFP4.set_kv_buffer, memory_pool.py:3062-3110: batched_quantize + two index
+ * writes per tensor): 16-bit k [n, Hkv*Dk] / v [n, Hkv*Dv] rows -> packed data and scale bytes at the layout addresses,
+ * one launch.  Arguments as rx_store_kv_fp8; head dims are multiples of 16.  The stored bytes equal the rule above bit
+ * for bit. */
+int rx_store_kv_mx4(const void* k, const void* v, const rx_kv_layout* lay /* HOST */, const rx_kv_mx4_scales* scales /* HOST */,
+                    const void* loc, int64_t n, int num_kv_heads, int head_dim, int v_head_dim, int64_t k_stride_t,
+                    int64_t v_stride_t, int src_dtype /* rx_dtype */, float k_scale, float v_scale, int loc_is_i64,
+                    int64_t size_limit, int64_t skip_index, int32_t* err_flag, void* stream);
+
+/* Decode attention over the 4-bit pool, nibbles and scale bytes read straight from HBM (replaces
+ * MHATokenToKVPoolFP4._get_key_buffer / _get_value_buffer, memory_pool.py:3029-3060 -- a dequantisation of the WHOLE
+ * layer per call -- followed by decode_attention_fwd).  p as for rx_decode_attn with p->kv the data buffers; head_dim ==
+ * v_head_dim in {64, 128}; both lookup modes; sm_scale, k_scale, v_scale, logit_cap, sinks, xai_temperature_len,
+ * request_order and the kv-split schedule (num_kv_splits / max_kv_splits with attn_logits / attn_lse, merged by the
+ * stage-2 kernels of rx_decode_attn; max_kv_splits == 1 or num_kv_splits == NULL writes o directly) behave as there.
+ * RX_ERR_UNSUPPORTED: k_new / v_new, rope_cos_sin, score_bias, kv_start, extra partials, split_items, unit_desc,
+ * merge_counters, stages != 0, the MLA shape and other head dims.  Data rows must be D/8-byte aligned, scale rows
+ * D/64-byte aligned.  rx_last_dispatch() names the decode_mx4_kernel instance. */
+int rx_decode_attn_mx4(const rx_decode_params* p /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, void* stream);
+
+/* The rows at loc[0:n] dequantised (exactly) into dense k_out [n, Hkv, Dk] / v_out [n, Hkv, Dv] of dst_dtype: the
+ * reference's dequantise-then-attend (memory_pool.py:3029-3060) restricted to the rows a batch needs -- an extend over
+ * a 4-bit prefix runs the 16-bit extend kernels on them with kv_indices = 0..n-1.  A slot outside [0, size_limit) gives
+ * zero rows and sets err_flag. */
+int rx_gather_kv_mx4(const rx_kv_layout* lay /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, const void* loc,
+                     int loc_is_i64, int64_t n, int num_kv_heads, int head_dim, int v_head_dim, void* k_out, void* v_out,
+                     int dst_dtype /* rx_dtype */, int64_t size_limit, int32_t* err_flag, void* stream);
+
 /* ---- shared-prefix (cascade) decode plan ----------------------------------------------------------
  * SURVEY 8f-2.  The reference has only the building block (merge_state); with RadixAttention every request
  * of a batch that hit the same radix-tree path carries the SAME leading slots in its req_to_token row

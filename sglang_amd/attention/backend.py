@@ -188,8 +188,10 @@ class HipRadixAttnBackend:
                 raise ValueError(f"DCP needs one kv head per rank (the replicated-kv-head case), got {self.num_kv_head}")
             self.num_head *= self.dcp.size
             decode_index_mode = "indices"  # the rank's share of a request is a strided subset of its row
-        self.v_head_dim = self.token_to_kv_pool.get_value_buffer(
-            getattr(self.token_to_kv_pool, "start_layer", 0)).shape[-1]
+        # a 4-bit (MXFP4) pool: decode reads its packed bytes (rx_decode_attn_mx4), an extend gathers its prefix rows
+        self._is_mx4_pool = isinstance(self.token_to_kv_pool, _own_pools.MHATokenToKVPoolFP4)
+        self.v_head_dim = (self.token_to_kv_pool.get_v_head_dim() if self._is_mx4_pool
+                           else self.token_to_kv_pool.get_value_buffer(getattr(self.token_to_kv_pool, "start_layer", 0)).shape[-1])
         self.max_context_len = mc.context_len
         sa = getattr(model_runner, "server_args", None)
         self.max_kv_splits = max_kv_splits or getattr(sa, "triton_attention_num_kv_splits", 8)
@@ -221,6 +223,10 @@ class HipRadixAttnBackend:
         if self.split_tile_size is not None:
             self.max_kv_splits = (self.max_context_len + self.split_tile_size - 1) // self.split_tile_size
         self.split_policy = split_policy
+        if self._is_mx4_pool and (cascade_decode or self.enable_deterministic or dcp is not None
+                                  or getattr(model_runner, "sliding_window_size", None)):
+            raise NotImplementedError("a 4-bit (MXFP4) KV pool serves the plain decode / extend paths: no cascade_decode, "
+                                      "deterministic inference, DCP or sliding-window layers")
         self.native_split_cap = 32
         # graph replay: upper bound of the fp32 kv-split partials [bs, Hq, slots, Dv] kept address-stable (bytes)
         self.graph_partials_budget = int(getattr(sa, "rx_graph_partials_budget", 256 << 20) or (256 << 20))
@@ -292,6 +298,8 @@ class HipRadixAttnBackend:
     def _split_dims(self):
         """(Dk, Dv) the split-KV extend forms serve for this pool, or None: head dim 128, or 16-bit latent MLA rows
         (576 / 512 over one kv head)."""
+        if self._is_mx4_pool:
+            return None
         if self._is_mla_pool:
             pool = self.token_to_kv_pool
             kb = pool.get_key_buffer(getattr(pool, "start_layer", 0))
@@ -1064,7 +1072,8 @@ class HipRadixAttnBackend:
         kernel itself -- one of OUR pools (or a foreign one that declares ``supports_fused_decode_store``: the fused
         store never calls its set_kv_buffer), a 16-bit pool of k's dtype, D = 64 / 128, at most 16 q heads per kv head, the plain or
         shared-prefix path (not DCP / sliding-window / scaled-store), 16-byte aligned rows."""
-        if self._no_fused_store or self.dcp is not None or self._is_mla_pool or not self._pool_allows_fused_store:
+        if (self._no_fused_store or self.dcp is not None or self._is_mla_pool or self._is_mx4_pool
+                or not self._pool_allows_fused_store):
             return False
         pool = self.token_to_kv_pool
         if getattr(pool, "is_fp8", False) or k.dtype != pool.dtype or v.dtype != pool.dtype:
@@ -1111,6 +1120,8 @@ class HipRadixAttnBackend:
         md = self.forward_metadata
         q3 = q.view(-1, layer.tp_q_head_num, layer.qk_head_dim)
         o3 = o.view(-1, layer.tp_q_head_num, layer.v_head_dim)
+        if self._is_mx4_pool:
+            return self._forward_decode_mx4(q3, o3, o, layer, forward_batch, md, sinks, score_mod)
         if self.dcp is not None:
             if score_mod is not None:
                 raise NotImplementedError("DCP decode does not support score_mod (as the reference, triton_backend.py:1798-1801)")
@@ -1202,6 +1213,27 @@ class HipRadixAttnBackend:
             ln(q3, o3, torch.cuda.current_stream(q.device).cuda_stream, sinks)
         return o
 
+    def _forward_decode_mx4(self, q3, o3, o, layer, fb: ForwardBatch, md, sinks, score_mod):
+        """Decode over a 4-bit pool: the plain split schedule (the bs x slots grid; split_items and the per-unit tables are
+        the 16-bit kernel's) and rx_decode_attn_mx4 on the packed bytes."""
+        if score_mod is not None:
+            raise NotImplementedError("score_mod is not supported on a 4-bit (MXFP4) KV pool")
+        if md.draft or (layer.sliding_window_size is not None and layer.sliding_window_size > -1):
+            raise NotImplementedError("draft decode / sliding-window layers are not supported on a 4-bit (MXFP4) KV pool")
+        k_descale, v_descale = self._scales(layer)
+        kb, vb, ksb, vsb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
+        splits = md.max_kv_splits if md.attn_logits is not None else 1
+        common = dict(logit_cap=layer.logit_cap, sinks=sinks, page_size=self.page_size, request_order=md.request_order,
+                      xai_temperature_len=max(0, int(getattr(layer, "xai_temperature_len", -1) or 0)),
+                      k_scale_buffer=ksb, v_scale_buffer=vsb)
+        if md.kv_indices is not None:
+            ops.decode_attention_fwd(q3, kb, vb, o3, md.kv_indptr, md.kv_indices, md.attn_logits, md.attn_lse, md.num_kv_splits,
+                                     splits, layer.scaling, k_descale, v_descale, **common)
+        else:
+            ops.decode_attention_fwd_paged(q3, kb, vb, o3, self.req_to_token, fb.req_pool_indices, fb.seq_lens, md.attn_logits,
+                                           md.attn_lse, md.num_kv_splits, splits, layer.scaling, k_descale, v_descale, **common)
+        return o
+
     def forward_extend(self, q, k, v, layer, forward_batch: ForwardBatch, save_kv_cache=True, sinks=None,
                        score_mod=None, aux_tensors=None):
         """triton_backend.py:1250-1437 (score_mod / aux_tensors: :1259-1260, :1348-1349, :1434-1435)."""
@@ -1235,6 +1267,23 @@ class HipRadixAttnBackend:
             return self._forward_extend_unified(q, o, layer, forward_batch, causal, sinks, score_mod, aux_tensors)
         md = self.forward_metadata
         k_descale, v_descale = self._scales(layer)
+        if self._is_mx4_pool:
+            # the prefix rows this batch reads are dequantised (exactly) into a dense 16-bit copy (rx_gather_kv_mx4) and the
+            # 16-bit extend runs on it; the new tokens' own K / V stay 16-bit, as in the reference
+            if score_mod is not None:
+                raise NotImplementedError("score_mod is not supported on a 4-bit (MXFP4) KV pool")
+            n_pre = int(sum(forward_batch.extend_prefix_lens_cpu)) if forward_batch.extend_prefix_lens_cpu is not None else None
+            idx = md.kv_indices if n_pre is None else md.kv_indices[:n_pre]
+            if idx.numel() == 0:  # no prefix anywhere: nothing is read from the pool
+                idx = torch.zeros(1, dtype=torch.int64, device=q.device)
+            k_buf, v_buf = self.token_to_kv_pool.gather(layer.layer_id, idx, q.dtype)
+            ops.extend_attention_fwd(
+                q.view(-1, layer.tp_q_head_num, layer.qk_head_dim), k.view(-1, layer.tp_k_head_num, layer.qk_head_dim),
+                v.view(-1, layer.tp_v_head_num, layer.v_head_dim), o.view(-1, layer.tp_q_head_num, layer.v_head_dim),
+                k_buf, v_buf, md.qo_indptr, md.kv_indptr, torch.arange(k_buf.shape[0], dtype=torch.int64, device=q.device),
+                md.custom_mask, causal, md.mask_indptr, md.max_extend_len, k_descale, v_descale, sm_scale=layer.scaling,
+                logit_cap=layer.logit_cap, sinks=sinks, xai_temperature_len=layer.xai_temperature_len, page_size=1)
+            return o
         k_buf, v_buf = self.token_to_kv_pool.get_kv_buffer(layer.layer_id)
         lay = ops.kv_layout_hnd(k_buf, v_buf) if getattr(self.token_to_kv_pool, "use_hnd", False) else None
         # sliding-window layers read the window indices (triton_backend.py:1353-1365)

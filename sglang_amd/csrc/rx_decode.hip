@@ -20,6 +20,7 @@
 //   * next tile's K/V loads are issued right after the current tile's operands are consumed,
 //     so every wave keeps ~16 KiB of HBM reads in flight under its softmax + PV work.
 #include "rx_common.h"
+#include "rx_decode_common.h"
 
 namespace rx {
 
@@ -80,13 +81,6 @@ struct DecodeArgs {
   const int32_t* first;
 };
 
-// Grok temperature factor of a request (decode_attention.py:156-160): the single query sits at seq_len-1
-__device__ __forceinline__ float xai_factor(int32_t xai_len, int32_t seq_len) {
-  const int32_t qidx = seq_len - 1;
-  if (xai_len <= 0 || qidx <= xai_len) return 1.0f;
-  return __log2f(static_cast<float>(qidx)) / __log2f(static_cast<float>(xai_len));
-}
-
 // Single-pass epilogue with extra partials (shared-prefix decode): folds the extras of (request b, head h),
 // column d, into the running (max in log2 units, sum, weighted value) of this workgroup's own pass -- what
 // stage 2 would do, without the fp32 partial round trip and the second launch.
@@ -133,31 +127,6 @@ __device__ unsigned long long g_dec_timeline[kTlMax * 6];
 #define RX_TL(slot) do {} while (0)
 #endif
 
-constexpr int kMinBlockKV = 32;  // decode_attention.py:36 (_MIN_BLOCK_KV)
-constexpr int kTile = 32;        // tokens per wave tile (K of the PV MFMA)
-constexpr int kWavesPerWG = 4;
-
-// XOR swizzle of the 16-byte chunk index inside a V row of the LDS tile.  Makes both the
-// ds_write_b128 of 8 consecutive rows and the ds_read_b64_tr_b16 of an 8-row x 32-byte
-// window conflict-free (bank = addr/4 mod 32 for writes, mod 64 for tr reads).
-template <int D>
-__device__ __forceinline__ int v_swizzle(int row) {
-  if constexpr (D == 64) return row & 7;
-  return ((row & 7) << 1) | ((row >> 2) & 1);
-}
-
-template <bool LINEAR>
-__device__ __forceinline__ int64_t slot_offset(int64_t slot, int32_t page_size,
-                                               int64_t page_stride, int64_t tok_stride) {
-  if constexpr (LINEAR) return mul_u32(slot, tok_stride);
-  // page_size < 0 encodes a power-of-two page: -(log2(page) + 1)  (shift/mask instead of div/mod)
-  if (page_size < 0) {
-    const int sh = -page_size - 1;
-    return mul_u32(slot >> sh, page_stride) + mul_u32(slot & ((1 << sh) - 1), tok_stride);
-  }
-  return (slot / page_size) * page_stride + (slot % page_size) * tok_stride;
-}
-
 struct SeqInfo {
   int32_t seq_len;   // tokens this launch attends
   int32_t full_len;  // the request's sequence length (position of the query + 1)
@@ -188,15 +157,6 @@ __device__ __forceinline__ SeqInfo seq_info(const DecodeArgs& a, int b) {
     s.idx = a.req_to_token + req * a.req_row_stride + start;  // IdxT == int32_t in this mode
   }
   return s;
-}
-
-__device__ __forceinline__ void split_range(int32_t seq_len, int32_t splits, int32_t split,
-                                            int32_t& lo, int32_t& hi) {
-  // decode_attention.py:466-472
-  const int32_t per =
-      ((seq_len + splits - 1) / splits + kMinBlockKV - 1) / kMinBlockKV * kMinBlockKV;
-  lo = per * split;
-  hi = min(lo + per, seq_len);
 }
 
 #ifndef RX_DEC_MINW

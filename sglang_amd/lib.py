@@ -30,6 +30,14 @@ class RxKvLayout(C.Structure):
     ]
 
 
+class RxKvMx4Scales(C.Structure):
+    _fields_ = [
+        ("k_scale_buf", c_void_p), ("v_scale_buf", c_void_p),
+        ("k_page_stride", c_int64), ("k_tok_stride", c_int64), ("k_head_stride", c_int64),
+        ("v_page_stride", c_int64), ("v_tok_stride", c_int64), ("v_head_stride", c_int64),
+    ]
+
+
 class RxPoolDesc(C.Structure):
     _fields_ = [("free_ring", c_void_p), ("release_ring", c_void_p), ("capacity", c_int64), ("flags", c_void_p),
                 ("num_ids", c_int64), ("tile_scratch", c_void_p), ("state", c_void_p)]
@@ -157,6 +165,13 @@ PROTOTYPES = {
     "rx_decode_attn": (c_int, [C.POINTER(RxDecodeParams), c_void_p]),
     "rx_decode_units": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    # 4-bit (MXFP4 block-16) KV pool
+    "rx_store_kv_mx4": (c_int, [c_void_p, c_void_p, C.POINTER(RxKvLayout), C.POINTER(RxKvMx4Scales), c_void_p, c_int64, c_int,
+                                c_int, c_int, c_int64, c_int64, c_int, C.c_float, C.c_float, c_int, c_int64, c_int64,
+                                c_void_p, c_void_p]),
+    "rx_decode_attn_mx4": (c_int, [C.POINTER(RxDecodeParams), C.POINTER(RxKvMx4Scales), c_void_p]),
+    "rx_gather_kv_mx4": (c_int, [C.POINTER(RxKvLayout), C.POINTER(RxKvMx4Scales), c_void_p, c_int, c_int64, c_int, c_int,
+                                 c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rx_extend_attn": (c_int, [C.POINTER(RxExtendParams), c_void_p]),
     "rx_alloc_extend": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "rx_alloc_decode": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),

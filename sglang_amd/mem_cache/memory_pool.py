@@ -229,6 +229,87 @@ class MHATokenToKVPool:
         return v
 
 
+class MHATokenToKVPoolFP4(MHATokenToKVPool):
+    """4-bit (MXFP4 block-16) K/V storage: MHATokenToKVPoolFP4 (memory_pool.py:2959-3110, --kv-cache-dtype fp4_e2m1) in
+    the format of FP4MXBlock16KVQuantizeUtil (include/radix_hip.h, "4-bit KV pool"): per layer uint8 ``k_buffer`` /
+    ``v_buffer`` [rows, Hkv, D/2] and ``k_scale_buffer`` / ``v_scale_buffer`` [rows, Hkv * D/16] (NHD, the reference's
+    shapes) or [pages, Hkv, page, D/2] / [pages, Hkv, page, D/16] (``use_hnd``).  ``dtype`` is the 16-bit dtype of the rows
+    that come in and of the rows ``gather`` hands out.  The attention kernels read the packed bytes (rx_decode_attn_mx4);
+    nothing ever dequantises a whole layer."""
+
+    fused_decode_store = False  # the decode kernel does not write this pool: the step's rows are quantised by the store
+
+    def _create_buffers(self):
+        if self.is_fp8 or self.head_dim % 16 or self.v_head_dim % 16:
+            raise NotImplementedError("MHATokenToKVPoolFP4: a 16-bit row dtype and head dims that are multiples of 16")
+        self.store_dtype = torch.uint8
+
+        def make(d, per):
+            if self.use_hnd:
+                shape = (self.num_pages, self.head_num, self.page_size, d // per)
+            else:
+                shape = ((self.size + self.page_size, self.head_num, d // 2) if per == 2
+                         else (self.size + self.page_size, self.head_num * d // 16))
+            return [torch.zeros(shape, dtype=torch.uint8, device=self.device) for _ in range(self.layer_num)]
+
+        self.k_buffer, self.v_buffer = make(self.head_dim, 2), make(self.v_head_dim, 2)
+        self.k_scale_buffer, self.v_scale_buffer = make(self.head_dim, 16), make(self.v_head_dim, 16)
+
+    def _build_ptr_tables(self):
+        """Data and scale buffers travel together (move_kv_cache copies rows of all four per layer)."""
+        bufs = self.k_buffer + self.v_buffer + self.k_scale_buffer + self.v_scale_buffer
+        self.data_ptrs = torch.tensor([b.data_ptr() for b in bufs], dtype=torch.int64, device=self.device)
+        self.data_strides = torch.tensor([b.stride(0) for b in bufs], dtype=torch.int64, device=self.device)
+        if self.use_hnd:
+            self.data_geom = torch.tensor([[b.stride(0), b.stride(1), b.stride(2), b.shape[3]] for b in bufs],
+                                          dtype=torch.int64, device=self.device)
+
+    def get_kv_size_bytes(self):
+        return (sum(b.numel() for b in self.k_buffer + self.k_scale_buffer),
+                sum(b.numel() for b in self.v_buffer + self.v_scale_buffer))
+
+    def get_key_buffer(self, layer_id: int):
+        raise NotImplementedError("MHATokenToKVPoolFP4 never dequantises a whole layer: attend the packed bytes "
+                                  "(get_mx4_buffers + ops.decode_attention_fwd(..., k_scale_buffer=, v_scale_buffer=)) or "
+                                  "gather the rows a batch needs (gather / ops.gather_kv_mx4)")
+
+    get_value_buffer = get_key_buffer
+
+    def get_kv_buffer(self, layer_id: int):
+        return self.get_key_buffer(layer_id)
+
+    def get_mx4_buffers(self, layer_id: int):
+        """(k data, v data, k scales, v scales) of a layer, packed bytes."""
+        li = layer_id - self.start_layer
+        return self.k_buffer[li], self.v_buffer[li], self.k_scale_buffer[li], self.v_scale_buffer[li]
+
+    def get_contiguous_buf_infos(self):
+        bufs = self.k_buffer + self.v_buffer + self.k_scale_buffer + self.v_scale_buffer
+        return [b.data_ptr() for b in bufs], [b.nbytes for b in bufs], [b[0].nbytes for b in bufs]
+
+    def set_kv_buffer(self, layer, loc_info, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                      k_scale: Optional[float] = None, v_scale: Optional[float] = None,
+                      layer_id_override: Optional[int] = None, dcp_kv_mask: Optional[torch.Tensor] = None):
+        """memory_pool.py:3062-3110: quantise and write, one launch (ops.store_cache_mx4)."""
+        loc, _, _ = unwrap_write_loc(loc_info)
+        if dcp_kv_mask is not None:
+            loc = torch.where(dcp_kv_mask.to(torch.bool), loc, torch.zeros_like(loc))
+        layer_id = layer_id_override if layer_id_override is not None else layer.layer_id
+        if cache_k.dtype != self.dtype:
+            cache_k, cache_v = cache_k.to(self.dtype), cache_v.to(self.dtype)
+        n = loc.shape[0]
+        kb, vb, ksb, vsb = self.get_mx4_buffers(layer_id)
+        ops.store_cache_mx4(cache_k.reshape(n, self.row_dim), cache_v.reshape(n, self.v_row_dim), kb, vb, ksb, vsb, loc,
+                            page_size=self.page_size, k_scale=1.0 if k_scale is None else float(k_scale),
+                            v_scale=1.0 if v_scale is None else float(v_scale), err_flag=self.err_flag)
+
+    def gather(self, layer_id: int, loc: torch.Tensor, dst_dtype: Optional[torch.dtype] = None):
+        """Dense 16-bit (k [n, Hkv, D], v [n, Hkv, Dv]) of the rows at ``loc`` (exact): an extend's prefix."""
+        kb, vb, ksb, vsb = self.get_mx4_buffers(layer_id)
+        return ops.gather_kv_mx4(kb, vb, ksb, vsb, loc, dst_dtype or self.dtype, page_size=self.page_size,
+                                 err_flag=self.err_flag)
+
+
 class MLATokenToKVPool:
     """Latent-KV pool for MLA models (memory_pool.py:3906-4179): ONE buffer per layer,
     [size + page_size, 1, kv_lora_rank + qk_rope_head_dim]; the value view is the first

@@ -126,6 +126,98 @@ def store_cache_fp8(k, v, layout: "_L.RxKvLayout", indices, num_kv_heads, head_d
     _L.check(st, "rx_store_kv_fp8")
 
 
+def _mx4_scales(k_scale_buffer: torch.Tensor, v_scale_buffer: torch.Tensor, page_size: int, hnd: bool) -> "_L.RxKvMx4Scales":
+    """rx_kv_mx4_scales of a 4-bit pool's scale buffers: NHD [slots, Hkv * D/16] (or [slots, Hkv, D/16]), HND [pages,
+    Hkv, page, D/16]; uint8, byte strides by the data buffers' convention."""
+    sc = _L.RxKvMx4Scales()
+    for name, buf in (("k", k_scale_buffer), ("v", v_scale_buffer)):
+        if buf.dtype != torch.uint8 or buf.stride(-1) != 1:
+            raise TypeError("4-bit pool: scale buffers are uint8, contiguous in their last dim")
+        if hnd:
+            if buf.dim() != 4:
+                raise ValueError("4-bit HND pool: scale buffers are [pages, Hkv, page, D/16]")
+            strides = (buf.stride(0), buf.stride(2), buf.stride(1))
+        else:
+            if buf.dim() not in (2, 3):
+                raise ValueError("4-bit NHD pool: scale buffers are [slots, Hkv * D/16]")
+            strides = (buf.stride(0) * page_size, buf.stride(0), buf.stride(1) if buf.dim() == 3 else 0)
+        setattr(sc, f"{name}_scale_buf", buf.data_ptr())
+        for fld, val in zip(("page", "tok", "head"), strides):
+            setattr(sc, f"{name}_{fld}_stride", val)
+    return sc
+
+
+def _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size: int):
+    """(layout, scales, Hkv, Dk, Dv, slots) of a 4-bit pool: data NHD [slots, Hkv, D/2] or HND [pages, Hkv, page, D/2]."""
+    for buf in (k_buffer, v_buffer):
+        if buf.dtype != torch.uint8 or buf.dim() not in (3, 4):
+            raise TypeError("4-bit pool: data buffers are uint8 [slots, Hkv, D/2] or [pages, Hkv, page, D/2]")
+    hnd = k_buffer.dim() == 4
+    lay = kv_layout_hnd(k_buffer, v_buffer) if hnd else _kv_layout(k_buffer, v_buffer, page_size)
+    sc = _mx4_scales(k_scale_buffer, v_scale_buffer, lay.page_size, hnd)
+    hkv, dk, dv = k_buffer.shape[1], 2 * k_buffer.shape[-1], 2 * v_buffer.shape[-1]
+    if not hnd and k_scale_buffer.dim() == 2:  # [slots, Hkv * D/16]: a head's scales are D/16 bytes apart
+        sc.k_head_stride, sc.v_head_stride = dk // 16, dv // 16
+    slots = k_buffer.shape[0] * (k_buffer.shape[2] if hnd else 1)
+    return lay, sc, hkv, dk, dv, slots
+
+
+def store_cache_mx4(k, v, k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, indices, *, page_size: int = 1,
+                    k_scale: float = 1.0, v_scale: float = 1.0, reserved_skip_index: int = 0, err_flag=None) -> None:
+    """Quantising KV store into a 4-bit (MXFP4 block-16) pool: MHATokenToKVPoolFP4.set_kv_buffer
+    (srt/mem_cache/memory_pool.py:3062-3110) with FP4MXBlock16KVQuantizeUtil.batched_quantize
+    (srt/layers/quantization/kvfp4_tensor.py:56-103) in one launch (rx_store_kv_mx4; include/radix_hip.h states the
+    format).  k [n, Hkv*Dk], v [n, Hkv*Dv] are 16-bit; the buffers NHD or HND (4-D)."""
+    _require_cuda(k, v, k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, indices)
+    k2, v2 = k.reshape(k.shape[0], -1), v.reshape(v.shape[0], -1)
+    if k2.stride(-1) != 1 or v2.stride(-1) != 1 or k2.dtype != v2.dtype:
+        raise ValueError("store_cache_mx4: k / v share one 16-bit dtype and are contiguous in their last dim")
+    lay, sc, hkv, dk, dv, slots = _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size)
+    if k2.shape[1] != hkv * dk or v2.shape[1] != hkv * dv or indices.numel() != k2.shape[0]:
+        raise ValueError("store_cache_mx4: k / v row width does not match the pool's [Hkv, D]; one index per row")
+    idx = indices if indices.is_contiguous() else indices.contiguous()
+    st = _L.load().rx_store_kv_mx4(_ptr(k2), _ptr(v2), C.byref(lay), C.byref(sc), _ptr(idx), k2.shape[0], hkv, dk, dv,
+                                   k2.stride(0), v2.stride(0), _rx_dtype(k2), float(k_scale), float(v_scale),
+                                   _is64(idx, "indices"), slots, reserved_skip_index, _ptr(err_flag), _stream(k2))
+    _L.check(st, "rx_store_kv_mx4")
+
+
+def gather_kv_mx4(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, indices, dst_dtype: torch.dtype, *, page_size: int = 1,
+                  err_flag=None):
+    """The rows of a 4-bit pool at ``indices``, dequantised exactly into dense (k [n, Hkv, Dk], v [n, Hkv, Dv]) of
+    dst_dtype (rx_gather_kv_mx4): what an extend over a 4-bit prefix attends, with kv_indices = arange(n) -- the
+    reference's whole-layer dequantisation (memory_pool.py:3029-3060) restricted to the rows the batch reads."""
+    _require_cuda(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, indices)
+    if dst_dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"gather_kv_mx4: dst_dtype {dst_dtype}")
+    lay, sc, hkv, dk, dv, slots = _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size)
+    n = indices.numel()
+    k_out = torch.empty((n, hkv, dk), dtype=dst_dtype, device=k_buffer.device)
+    v_out = torch.empty((n, hkv, dv), dtype=dst_dtype, device=k_buffer.device)
+    idx = indices if indices.is_contiguous() else indices.contiguous()
+    st = _L.load().rx_gather_kv_mx4(C.byref(lay), C.byref(sc), _ptr(idx), _is64(idx, "indices"), n, hkv, dk, dv, _ptr(k_out),
+                                    _ptr(v_out), _L.RX_BF16 if dst_dtype == torch.bfloat16 else _L.RX_F16, slots,
+                                    _ptr(err_flag), _stream(k_buffer))
+    _L.check(st, "rx_gather_kv_mx4")
+    return k_out, v_out
+
+
+def _mx4_decode(p, q, k_buffer, v_buffer, k_scale_buffer, v_scale_buffer) -> None:
+    """The decode call of a 4-bit pool (rx_decode_attn_mx4): p is filled as for rx_decode_attn, p.kv the data buffers."""
+    lay, sc, hkv, dk, dv, _ = _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, p.kv.page_size)
+    if (dk, dv) != (p.head_dim, p.v_head_dim):
+        raise ValueError(f"4-bit pool rows hold {dk} / {dv} elements, q / o {p.head_dim} / {p.v_head_dim}")
+    p.kv, p.num_kv_heads = lay, hkv
+    _L.check(_L.load().rx_decode_attn_mx4(C.byref(p), C.byref(sc), _stream(q)), "rx_decode_attn_mx4")
+
+
+def _mx4_reject(**given) -> None:
+    """A 4-bit pool serves the plain split schedule only: every other option raises, naming the argument."""
+    for name, val in given.items():
+        if val is not None and not (isinstance(val, int) and val == 0):
+            raise NotImplementedError(f"{name} is not supported on a 4-bit (MXFP4) KV pool")
+
+
 def fused_fp8_qkv_kv_cache(q: Optional[torch.Tensor], k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor,
                            v_cache: torch.Tensor, cache_loc: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
                            v_scale: Optional[torch.Tensor] = None, *, kv_layout=None, page_size: int = 1,
@@ -509,12 +601,20 @@ def decode_attention_fwd(q, k_buffer, v_buffer, o, kv_indptr, kv_indices, attn_l
                          num_kv_splits, max_kv_splits, sm_scale, k_scale, v_scale, logit_cap=0.0,
                          sinks=None, xai_temperature_len=-1, has_mla=False, use_pdl=False,
                          page_size: int = 1, score_mod=None, aux_tensors=None, kv_layout=None, stages: int = 0,
-                         merge_counters=None, k_new=None, v_new=None, request_order=None, split_items=None):
+                         merge_counters=None, k_new=None, v_new=None, request_order=None, split_items=None,
+                         k_scale_buffer=None, v_scale_buffer=None):
     """Same contract as the reference.  q [bs,Hq,Dk], o [bs,Hq,Dv], kv_indptr int32[bs+1],
     kv_indices int32/int64, attn_logits fp32[bs,Hq,max_kv_splits,Dv], attn_lse fp32[bs,Hq,S].
     ``max_kv_splits == 1`` (or num_kv_splits None) runs the single-pass kernel.  ``stages`` as in
     rx_decode_params (1 = the kv-split partials only).  ``score_mod`` = relative_bias_score_mod with
-    ``aux_tensors = [rel_logits [bs, Hq, extent]]`` (decode_attention.py:215-227,539-551)."""
+    ``aux_tensors = [rel_logits [bs, Hq, extent]]`` (decode_attention.py:215-227,539-551).  ``k_scale_buffer`` /
+    ``v_scale_buffer``: k_buffer / v_buffer are the data bytes of a 4-bit (MXFP4 block-16) pool and these its scale bytes
+    (rx_decode_attn_mx4): the plain split schedule only, every other option raises NotImplementedError."""
+    mx4 = k_scale_buffer is not None or v_scale_buffer is not None
+    if mx4:
+        _mx4_reject(score_mod=score_mod, stages=stages, merge_counters=merge_counters, k_new=k_new, v_new=v_new,
+                    split_items=split_items)
+        kv_layout = kv_layout_hnd(k_buffer, v_buffer) if k_buffer.dim() == 4 else None  # (HND: the 4-D buffers say so)
     # has_mla only selects a Triton block shape in the reference; here the MLA kernel is chosen from the
     # tensor shapes (Dk 576 / Dv 512, one kv head, V aliasing K)
     _require_cuda(q, k_buffer, v_buffer, o, kv_indptr, kv_indices)
@@ -538,6 +638,8 @@ def decode_attention_fwd(q, k_buffer, v_buffer, o, kv_indptr, kv_indices, attn_l
     _set_new_kv(p, k_new, v_new, q.shape[0])
     p.request_order = _request_order_ptr(request_order, q.shape[0])
     _set_split_items(p, split_items if p.max_kv_splits > 1 else None)
+    if mx4:
+        return _mx4_decode(p, q, k_buffer, v_buffer, k_scale_buffer, v_scale_buffer)
     _L.check(_L.load().rx_decode_attn(C.byref(p), _stream(q)), "rx_decode_attn")
 
 
@@ -749,7 +851,13 @@ def decode_attention_fwd_paged(q, k_buffer, v_buffer, o, req_to_token, req_pool_
                                page_size: int = 1, kv_layout=None, xai_temperature_len=-1,
                                kv_start=None, extra_o=None, extra_lse=None, stages: int = 0, merge_counters=None,
                                k_new=None, v_new=None, request_order=None, split_items=None,
-                               score_mod=None, aux_tensors=None, units=None):
+                               score_mod=None, aux_tensors=None, units=None, k_scale_buffer=None, v_scale_buffer=None):
+    """``k_scale_buffer`` / ``v_scale_buffer``: a 4-bit (MXFP4 block-16) pool, as in decode_attention_fwd."""
+    mx4 = k_scale_buffer is not None or v_scale_buffer is not None
+    if mx4:
+        _mx4_reject(kv_start=kv_start, extra_o=extra_o, extra_lse=extra_lse, stages=stages, merge_counters=merge_counters,
+                    k_new=k_new, v_new=v_new, split_items=split_items, score_mod=score_mod, units=units)
+        kv_layout = kv_layout_hnd(k_buffer, v_buffer) if k_buffer.dim() == 4 else None  # (HND: the 4-D buffers say so)
     p = _decode_paged_params(q, k_buffer, v_buffer, o, req_to_token, req_pool_indices, seq_lens, attn_logits, attn_lse,
                              num_kv_splits, max_kv_splits, sm_scale, k_scale, v_scale, logit_cap, sinks, page_size,
                              kv_layout, xai_temperature_len, kv_start, extra_o, extra_lse, stages)
@@ -760,6 +868,8 @@ def decode_attention_fwd_paged(q, k_buffer, v_buffer, o, req_to_token, req_pool_
     _set_score_bias(p, score_mod, aux_tensors, q)
     _set_units(p, units)
     p._keep_units = units
+    if mx4:
+        return _mx4_decode(p, q, k_buffer, v_buffer, k_scale_buffer, v_scale_buffer)
     _L.check(_L.load().rx_decode_attn(C.byref(p), _stream(q)), "rx_decode_attn")
 
 
