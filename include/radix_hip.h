@@ -484,7 +484,7 @@ int rx_store_kv_mx4(const void* k, const void* v, const rx_kv_layout* lay /* HOS
  * request_order and the kv-split schedule (num_kv_splits / max_kv_splits with attn_logits / attn_lse, merged by the
  * stage-2 kernels of rx_decode_attn; max_kv_splits == 1 or num_kv_splits == NULL writes o directly) behave as there.
  * RX_ERR_UNSUPPORTED: k_new / v_new, rope_cos_sin, score_bias, kv_start, extra partials, split_items, unit_desc,
- * merge_counters, stages != 0, the MLA shape and other head dims.  Data rows must be D/8-byte aligned, scale rows
+ * merge_counters, stages != 0 and other head dims (latent rows 576 / 512: below).  Data rows must be D/8-byte aligned, scale rows
  * D/64-byte aligned.  rx_last_dispatch() names the decode_mx4_kernel instance. */
 int rx_decode_attn_mx4(const rx_decode_params* p /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, void* stream);
 
@@ -495,6 +495,33 @@ int rx_decode_attn_mx4(const rx_decode_params* p /* HOST */, const rx_kv_mx4_sca
 int rx_gather_kv_mx4(const rx_kv_layout* lay /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, const void* loc,
                      int loc_is_i64, int64_t n, int num_kv_heads, int head_dim, int v_head_dim, void* k_out, void* v_out,
                      int dst_dtype /* rx_dtype */, int64_t size_limit, int32_t* err_flag, void* stream);
+
+/* Latent (MLA) rows in the same format: MLATokenToKVPoolFP4 (srt/mem_cache/memory_pool.py:4182-4319), ONE data buffer
+ * [slots, 1, (rank + rope) / 2] and ONE scale buffer [slots, (rank + rope) / 16] -- 288 + 36 = 324 B per token at 512 + 64.
+ * Both widths are multiples of 16, so quantising nope and rope separately (as the reference does) equals quantising the
+ * concatenated row.  The entry points below read only the k_* fields of lay / scales.
+ *
+ * Decode: rx_decode_attn_mx4 with head_dim 576, v_head_dim 512, one kv head and v_buf / v_scale_buf aliasing k_buf /
+ * k_scale_buf (same strides) runs rx::decode_mla_mx4_kernel (rx_decode_mla_mx4.hip) in place of get_key_buffer's
+ * batched_dequantize of the whole layer (memory_pool.py:4220-4239) + the 16-bit decode.  Options and restrictions as
+ * above (request_order is accepted and ignored, as by the 16-bit latent kernel); data rows 16-byte aligned, scale rows
+ * 2-byte aligned.  rx_last_dispatch() names "decode_mla_mx4_kernel<T, IdxT, LINEAR>|indices" or "...|req_to_token".
+ *
+ * rx_store_mla_mx4 (set_kv_buffer / set_mla_kv_buffer, memory_pool.py:4241-4319): n rows quantised and written in one
+ * launch.  rope == NULL: nope_or_row holds the whole (kv_lora_rank + rope_dim)-wide row; else the [nope | rope] pair from
+ * two pointers.  Strides in elements; semantics as rx_store_kv_mx4 (ties up, zero block -> scale byte 94, skip_index
+ * skipped, a slot outside [0, size_limit) dropped and flagged). */
+int rx_store_mla_mx4(const void* nope_or_row, const void* rope, const rx_kv_layout* lay /* HOST */,
+                     const rx_kv_mx4_scales* scales /* HOST */, const void* loc, int64_t n, int kv_lora_rank, int rope_dim,
+                     int64_t nope_stride_t, int64_t rope_stride_t, int src_dtype /* rx_dtype */, float scale, int loc_is_i64,
+                     int64_t size_limit, int64_t skip_index, int32_t* err_flag, void* stream);
+
+/* get_mla_kv_buffer on that pool (memory_pool.py:4117-4138 over the dequantised layer): the rows at loc[0:n] dequantised
+ * (exactly) into dense nope_out [n, kv_lora_rank] / rope_out [n, rope_dim] of dst_dtype.  A slot outside [0, size_limit)
+ * gives zero rows and sets err_flag. */
+int rx_gather_mla_mx4(const rx_kv_layout* lay /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, const void* loc,
+                      int loc_is_i64, int64_t n, int kv_lora_rank, int rope_dim, void* nope_out, void* rope_out,
+                      int dst_dtype /* rx_dtype */, int64_t size_limit, int32_t* err_flag, void* stream);
 
 /* ---- shared-prefix (cascade) decode plan ----------------------------------------------------------
  * SURVEY 8f-2.  The reference has only the building block (merge_state); with RadixAttention every request

@@ -189,7 +189,9 @@ class HipRadixAttnBackend:
             self.num_head *= self.dcp.size
             decode_index_mode = "indices"  # the rank's share of a request is a strided subset of its row
         # a 4-bit (MXFP4) pool: decode reads its packed bytes (rx_decode_attn_mx4), an extend gathers its prefix rows
-        self._is_mx4_pool = isinstance(self.token_to_kv_pool, _own_pools.MHATokenToKVPoolFP4)
+        # (latent rows, MLATokenToKVPoolFP4: the same routes over decode_mla_mx4_kernel / rx_gather_mla_mx4)
+        self._is_mla_mx4_pool = isinstance(self.token_to_kv_pool, _own_pools.MLATokenToKVPoolFP4)
+        self._is_mx4_pool = self._is_mla_mx4_pool or isinstance(self.token_to_kv_pool, _own_pools.MHATokenToKVPoolFP4)
         self.v_head_dim = (self.token_to_kv_pool.get_v_head_dim() if self._is_mx4_pool
                            else self.token_to_kv_pool.get_value_buffer(getattr(self.token_to_kv_pool, "start_layer", 0)).shape[-1])
         self.max_context_len = mc.context_len
@@ -225,8 +227,9 @@ class HipRadixAttnBackend:
         self.split_policy = split_policy
         if self._is_mx4_pool and (cascade_decode or self.enable_deterministic or dcp is not None
                                   or getattr(model_runner, "sliding_window_size", None)):
-            raise NotImplementedError("a 4-bit (MXFP4) KV pool serves the plain decode / extend paths: no cascade_decode, "
-                                      "deterministic inference, DCP or sliding-window layers")
+            raise NotImplementedError(f"a 4-bit (MXFP4) KV pool ({type(self.token_to_kv_pool).__name__}) serves the plain "
+                                      "decode / extend paths: no cascade_decode, deterministic inference, DCP or "
+                                      "sliding-window layers")
         self.native_split_cap = 32
         # graph replay: upper bound of the fp32 kv-split partials [bs, Hq, slots, Dv] kept address-stable (bytes)
         self.graph_partials_budget = int(getattr(sa, "rx_graph_partials_budget", 256 << 20) or (256 << 20))
@@ -1216,12 +1219,17 @@ class HipRadixAttnBackend:
     def _forward_decode_mx4(self, q3, o3, o, layer, fb: ForwardBatch, md, sinks, score_mod):
         """Decode over a 4-bit pool: the plain split schedule (the bs x slots grid; split_items and the per-unit tables are
         the 16-bit kernel's) and rx_decode_attn_mx4 on the packed bytes."""
+        name = type(self.token_to_kv_pool).__name__
         if score_mod is not None:
-            raise NotImplementedError("score_mod is not supported on a 4-bit (MXFP4) KV pool")
+            raise NotImplementedError(f"score_mod is not supported on a 4-bit (MXFP4) KV pool ({name})")
         if md.draft or (layer.sliding_window_size is not None and layer.sliding_window_size > -1):
-            raise NotImplementedError("draft decode / sliding-window layers are not supported on a 4-bit (MXFP4) KV pool")
+            raise NotImplementedError(f"draft decode / sliding-window layers are not supported on a 4-bit (MXFP4) KV pool ({name})")
         k_descale, v_descale = self._scales(layer)
-        kb, vb, ksb, vsb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
+        if self._is_mla_mx4_pool:  # one latent buffer: V is the first 512 columns of the same bytes
+            kb, ksb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
+            vb, vsb = kb, None
+        else:
+            kb, vb, ksb, vsb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
         splits = md.max_kv_splits if md.attn_logits is not None else 1
         common = dict(logit_cap=layer.logit_cap, sinks=sinks, page_size=self.page_size, request_order=md.request_order,
                       xai_temperature_len=max(0, int(getattr(layer, "xai_temperature_len", -1) or 0)),
@@ -1276,7 +1284,14 @@ class HipRadixAttnBackend:
             idx = md.kv_indices if n_pre is None else md.kv_indices[:n_pre]
             if idx.numel() == 0:  # no prefix anywhere: nothing is read from the pool
                 idx = torch.zeros(1, dtype=torch.int64, device=q.device)
-            k_buf, v_buf = self.token_to_kv_pool.gather(layer.layer_id, idx, q.dtype)
+            if self._is_mla_mx4_pool:  # (as fp8 latent rows below: a dense 16-bit copy for extend_mla_kernel)
+                nope, rope = self.token_to_kv_pool.get_mla_kv_buffer(layer, idx, dst_dtype=q.dtype)
+                k_buf = torch.cat([nope, rope], dim=-1)
+                v_buf = k_buf[..., : layer.v_head_dim]
+                if self.mla_v_is_latent_prefix and k.shape[-1] == layer.tp_k_head_num * layer.qk_head_dim:
+                    v = k.view(-1, layer.tp_k_head_num, layer.qk_head_dim)[..., : layer.v_head_dim]
+            else:
+                k_buf, v_buf = self.token_to_kv_pool.gather(layer.layer_id, idx, q.dtype)
             ops.extend_attention_fwd(
                 q.view(-1, layer.tp_q_head_num, layer.qk_head_dim), k.view(-1, layer.tp_k_head_num, layer.qk_head_dim),
                 v.view(-1, layer.tp_v_head_num, layer.v_head_dim), o.view(-1, layer.tp_q_head_num, layer.v_head_dim),

@@ -21,6 +21,7 @@
 //     DEPTH tiles per wave in flight (4 x 8 waves x 4.5 KiB = 144 KiB per CU at two workgroups per CU).
 #include "rx_common.h"
 #include "rx_decode_common.h"
+#include "rx_mx4_common.h"
 
 namespace rx {
 
@@ -28,28 +29,7 @@ namespace rx {
 #define RX_MX4_DEPTH 4  // K/V register sets (tiles in flight per wave) of decode_mx4_kernel
 #endif
 
-// ---- the format -------------------------------------------------------------------------------------------------------
-// 2^(scale byte - 127) as the f32 operand of the scaled converts
-__device__ __forceinline__ float mx4_scale_f32(uint32_t byte) { return __builtin_bit_cast(float, byte << 23); }
-
-// one dword = eight e2m1 nibbles (element 2 i in the low nibble of byte i) -> eight 16-bit floats of T, times `scale`
-template <typename T>
-__device__ __forceinline__ u32x4 mx4x8_to_16(uint32_t dw, float scale) {
-  u32x4 out;
-  if constexpr (__is_same(typename T::scalar, __bf16)) {
-    out[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 0));
-    out[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 1));
-    out[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 2));
-    out[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 3));
-  } else {
-    out[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 0));
-    out[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 1));
-    out[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 2));
-    out[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 3));
-  }
-  return out;
-}
-
+// ---- the format (the unpack: rx_mx4_common.h) ---------------------------------------------------------------------------
 // One block of 16 source elements (two 16-byte loads) -> 8 data bytes + its scale byte: batched_quantize
 // (kvfp4_tensor.py:56-103) evaluated in fp32.  e = max(-33, ceil(log2(max / 6))) comes from the maximum's exponent and
 // mantissa (mantissa <= 1.5: E - 2, else E - 1), the magnitude code is the count of the bounds <= |x / 2^e| (ties go UP in
@@ -86,13 +66,6 @@ __device__ __forceinline__ u32x2 mx4_quant16(u32x4 lo, u32x4 hi, float scale, ui
   }
   return out;
 }
-
-struct Mx4Pool {  // a data buffer and its scale buffer, byte strides
-  uint8_t* data;
-  uint8_t* scales;
-  int64_t dps, dts, dhs;  // data page / token / head stride
-  int64_t sps, sts, shs;  // scales
-};
 
 // ---- rx_store_kv_mx4: one wave per token, one 16-element block per lane and step ---------------------------------------
 // Consecutive lanes own consecutive blocks of the row: their 8-byte data stores and their scale bytes are contiguous
@@ -466,16 +439,6 @@ static void launch_decode_mx4(const Mx4DecodeArgs& a, bool idx64, bool linear, h
 #undef RX_MX4
 }
 
-static Mx4Pool mx4_pool(const void* data, const void* scales, int64_t dps, int64_t dts, int64_t dhs, int64_t sps, int64_t sts,
-                        int64_t shs) {
-  Mx4Pool p;
-  p.data = static_cast<uint8_t*>(const_cast<void*>(data));
-  p.scales = static_cast<uint8_t*>(const_cast<void*>(scales));
-  p.dps = dps; p.dts = dts; p.dhs = dhs;
-  p.sps = sps; p.sts = sts; p.shs = shs;
-  return p;
-}
-
 // the layout's checks shared by the three entry points: D in units the kernels' vector accesses need
 static int mx4_check_layout(const char* who, const rx_kv_layout* lay, const rx_kv_mx4_scales* sc, int dk, int dv) {
   RX_REQUIRE(lay && sc && lay->k_buf && lay->v_buf && sc->k_scale_buf && sc->v_scale_buf, "%s: null layout / buffer", who);
@@ -545,6 +508,76 @@ extern "C" int rx_gather_kv_mx4(const rx_kv_layout* lay, const rx_kv_mx4_scales*
   return check_launch("rx_gather_kv_mx4");
 }
 
+namespace rx {
+int launch_decode_mla_mx4(const rx_decode_params* p, const rx_kv_mx4_scales* sc, int max_splits, hipStream_t s);  // rx_decode_mla_mx4.hip
+}
+
+// A one-tensor (latent) pool: the row [nope | rope] is ONE buffer of (rank + rope_dim) / 2 data bytes and (rank + rope_dim) / 16
+// scale bytes.  Both widths are multiples of 16, so no block straddles the seam and the two-tensor kernels serve it as they
+// are: "K" = the nope part, "V" = the rope part rank / 2 data bytes (rank / 16 scale bytes) further into the same row -- or
+// the whole row as K and an empty V.
+static int mla_pool_pair(const char* who, const rx_kv_layout* lay, const rx_kv_mx4_scales* sc, int rank, int rope_dim, Mx4Pool& kp,
+                         Mx4Pool& vp) {
+  RX_REQUIRE(lay && sc && lay->k_buf && sc->k_scale_buf, "%s: null layout / buffer", who);
+  RX_REQUIRE(lay->page_size >= 1, "%s: page_size < 1", who);
+  RX_REQUIRE(rank > 0 && rope_dim >= 0 && rank % 16 == 0 && rope_dim % 16 == 0, "%s: kv_lora_rank / rope_dim must be multiples of 16", who);
+  RX_REQUIRE((lay->k_page_stride | lay->k_tok_stride | (int64_t)(uintptr_t)lay->k_buf) % 8 == 0,
+             "%s: the data buffer and its byte strides must be multiples of 8", who);
+  kp = mx4_pool(lay->k_buf, sc->k_scale_buf, lay->k_page_stride, lay->k_tok_stride, 0, sc->k_page_stride, sc->k_tok_stride, 0);
+  vp = kp;
+  vp.data += rank / 2;
+  vp.scales += rank / 16;
+  return RX_OK;
+}
+
+extern "C" int rx_store_mla_mx4(const void* nope_or_row, const void* rope, const rx_kv_layout* lay, const rx_kv_mx4_scales* sc,
+                                const void* loc, int64_t n, int kv_lora_rank, int rope_dim, int64_t nope_stride_t,
+                                int64_t rope_stride_t, int src_dtype, float scale, int loc_is_i64, int64_t size_limit,
+                                int64_t skip_index, int32_t* err_flag, void* stream) {
+  RX_RANGE("rx_store_mla_mx4");
+  RX_REQUIRE(n >= 0, "rx_store_mla_mx4: n < 0");
+  if (n == 0) return RX_OK;
+  RX_REQUIRE(nope_or_row && loc, "rx_store_mla_mx4: null pointer");
+  Mx4Pool kp, vp;
+  if (const int rc = mla_pool_pair("rx_store_mla_mx4", lay, sc, kv_lora_rank, rope_dim, kp, vp)) return rc;
+  RX_REQUIRE(src_dtype == RX_BF16 || src_dtype == RX_F16, "rx_store_mla_mx4: src_dtype %d", src_dtype);
+  RX_REQUIRE(size_limit > 0 && scale > 0.f, "rx_store_mla_mx4: size_limit and scale must be positive");
+  RX_REQUIRE((nope_stride_t | (rope ? rope_stride_t : 0)) % 8 == 0 && (((uintptr_t)nope_or_row | (uintptr_t)rope) % 16 == 0),
+             "rx_store_mla_mx4: source rows must be 16-byte aligned");
+  // rope == NULL: nope_or_row is the whole (rank + rope_dim)-wide row
+  const int dk = rope ? kv_lora_rank : kv_lora_rank + rope_dim, dv = rope ? rope_dim : 0;
+#define RX_SQ(TT)                                                                                                              \
+  hipLaunchKernelGGL(store_kv_mx4_kernel<TT>, dim3(static_cast<unsigned>((n + 3) / 4)), dim3(256), 0,                          \
+                     static_cast<hipStream_t>(stream), (const uint16_t*)nope_or_row, (const uint16_t*)rope, kp, vp, loc, n, 1, dk, \
+                     dv, nope_stride_t, rope_stride_t, lay->page_size, scale, scale, loc_is_i64, size_limit, skip_index, err_flag)
+  if (src_dtype == RX_BF16) RX_SQ(BF16);
+  else RX_SQ(F16);
+#undef RX_SQ
+  return check_launch("rx_store_mla_mx4");
+}
+
+extern "C" int rx_gather_mla_mx4(const rx_kv_layout* lay, const rx_kv_mx4_scales* sc, const void* loc, int loc_is_i64, int64_t n,
+                                 int kv_lora_rank, int rope_dim, void* nope_out, void* rope_out, int dst_dtype, int64_t size_limit,
+                                 int32_t* err_flag, void* stream) {
+  RX_RANGE("rx_gather_mla_mx4");
+  RX_REQUIRE(n >= 0, "rx_gather_mla_mx4: n < 0");
+  if (n == 0) return RX_OK;
+  RX_REQUIRE(loc && nope_out && (rope_out || rope_dim == 0), "rx_gather_mla_mx4: null pointer");
+  Mx4Pool kp, vp;
+  if (const int rc = mla_pool_pair("rx_gather_mla_mx4", lay, sc, kv_lora_rank, rope_dim, kp, vp)) return rc;
+  RX_REQUIRE(dst_dtype == RX_BF16 || dst_dtype == RX_F16, "rx_gather_mla_mx4: dst_dtype %d", dst_dtype);
+  RX_REQUIRE(size_limit > 0, "rx_gather_mla_mx4: size_limit must be positive");
+  RX_REQUIRE((((uintptr_t)nope_out | (uintptr_t)rope_out) % 16) == 0, "rx_gather_mla_mx4: outputs must be 16-byte aligned");
+#define RX_GQ(TT)                                                                                                            \
+  hipLaunchKernelGGL(gather_kv_mx4_kernel<TT>, dim3(static_cast<unsigned>((n + 3) / 4)), dim3(256), 0,                       \
+                     static_cast<hipStream_t>(stream), kp, vp, loc, n, 1, kv_lora_rank, rope_dim, lay->page_size,            \
+                     (uint16_t*)nope_out, (uint16_t*)rope_out, loc_is_i64, size_limit, err_flag)
+  if (dst_dtype == RX_BF16) RX_GQ(BF16);
+  else RX_GQ(F16);
+#undef RX_GQ
+  return check_launch("rx_gather_mla_mx4");
+}
+
 static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scales* sc, void* stream) {
   RX_REQUIRE(p, "rx_decode_attn_mx4: params is null");
   RX_REQUIRE(sc, "rx_decode_attn_mx4: scales is null");
@@ -555,8 +588,10 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
              "rx_decode_attn_mx4: Hq=%d must be a positive multiple of Hkv=%d", p->num_q_heads, p->num_kv_heads);
   RX_REQUIRE(p->dtype == RX_BF16 || p->dtype == RX_F16, "rx_decode_attn_mx4: dtype %d", p->dtype);
   const int dk = p->head_dim, dv = p->v_head_dim;
-  if (!(dk == dv && (dk == 64 || dk == 128)))
-    return fail(RX_ERR_UNSUPPORTED, "rx_decode_attn_mx4: head dims %d / %d (64 or 128; not the MLA shape)", dk, dv);
+  const bool mla = dk == 576 && dv == 512 && p->num_kv_heads == 1;  // latent rows: decode_mla_mx4_kernel
+  if (!mla && !(dk == dv && (dk == 64 || dk == 128)))
+    return fail(RX_ERR_UNSUPPORTED, "rx_decode_attn_mx4: head dims %d / %d (64 or 128, or latent rows 576 / 512 with one kv head)",
+                dk, dv);
 #define RX_MX4_NO(cond, what) \
   if (cond) return fail(RX_ERR_UNSUPPORTED, "rx_decode_attn_mx4: " what " is not supported on a 4-bit pool")
   RX_MX4_NO(p->k_new || p->v_new, "the fused store (k_new / v_new)");
@@ -585,10 +620,14 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
                        p->kv.v_tok_stride | p->kv.v_head_stride | (uintptr_t)p->kv.k_buf | (uintptr_t)p->kv.v_buf;
   const int64_t sall = sc->k_page_stride | sc->k_tok_stride | sc->k_head_stride | sc->v_page_stride | sc->v_tok_stride |
                        sc->v_head_stride | (uintptr_t)sc->k_scale_buf | (uintptr_t)sc->v_scale_buf;
-  RX_REQUIRE(dall % (dk / 8) == 0 && sall % (dk / 64) == 0,
+  RX_REQUIRE(mla || (dall % (dk / 8) == 0 && sall % (dk / 64) == 0),
              "rx_decode_attn_mx4: data rows must be %d-byte aligned, scale rows %d-byte aligned", dk / 8, dk / 64);
   RX_REQUIRE((p->q_stride_t | p->q_stride_h) % 8 == 0 && ((uintptr_t)p->q & 15) == 0,
              "rx_decode_attn_mx4: q rows must be 16-byte aligned");
+  auto s = static_cast<hipStream_t>(stream);
+  if (mla) {
+    if (const int rc = launch_decode_mla_mx4(p, sc, max_splits, s)) return rc;
+  } else {
   Mx4DecodeArgs a;
   a.q = (const uint16_t*)p->q;
   a.o = (uint16_t*)p->o;
@@ -627,13 +666,13 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
   const bool linear = ps == 1 || (p->kv.k_page_stride == ps * p->kv.k_tok_stride && p->kv.v_page_stride == ps * p->kv.v_tok_stride &&
                                   sc->k_page_stride == ps * sc->k_tok_stride && sc->v_page_stride == ps * sc->v_tok_stride);
   const bool idx64 = mode_a && p->kv_indices_is_i64;
-  auto s = static_cast<hipStream_t>(stream);
   if (p->dtype == RX_BF16) {
     if (dk == 64) launch_decode_mx4<BF16, 64>(a, idx64, linear, s);
     else launch_decode_mx4<BF16, 128>(a, idx64, linear, s);
   } else {
     if (dk == 64) launch_decode_mx4<F16, 64>(a, idx64, linear, s);
     else launch_decode_mx4<F16, 128>(a, idx64, linear, s);
+  }
   }
   if (const int rc = check_launch("rx_decode_attn_mx4")) return rc;
   if (max_splits == 1) return RX_OK;

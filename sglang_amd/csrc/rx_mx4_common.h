@@ -1,0 +1,46 @@
+// The 4-bit (MXFP4 block-16) format's device helpers shared by rx_kv_mx4.hip and rx_decode_mla_mx4.hip: the exact
+// unpack in registers and the (data, scales) buffer pair.  include/radix_hip.h "4-bit KV pool" states the format.
+#pragma once
+#include "rx_common.h"
+
+namespace rx {
+
+// 2^(scale byte - 127) as the f32 operand of the scaled converts
+__device__ __forceinline__ float mx4_scale_f32(uint32_t byte) { return __builtin_bit_cast(float, byte << 23); }
+
+// one dword = eight e2m1 nibbles (element 2 i in the low nibble of byte i) -> eight 16-bit floats of T, times `scale`
+template <typename T>
+__device__ __forceinline__ u32x4 mx4x8_to_16(uint32_t dw, float scale) {
+  u32x4 out;
+  if constexpr (__is_same(typename T::scalar, __bf16)) {
+    out[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 0));
+    out[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 1));
+    out[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 2));
+    out[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 3));
+  } else {
+    out[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 0));
+    out[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 1));
+    out[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 2));
+    out[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(dw, scale, 3));
+  }
+  return out;
+}
+
+struct Mx4Pool {  // a data buffer and its scale buffer, byte strides
+  uint8_t* data;
+  uint8_t* scales;
+  int64_t dps, dts, dhs;  // data page / token / head stride
+  int64_t sps, sts, shs;  // scales
+};
+
+inline Mx4Pool mx4_pool(const void* data, const void* scales, int64_t dps, int64_t dts, int64_t dhs, int64_t sps, int64_t sts,
+                        int64_t shs) {
+  Mx4Pool p;
+  p.data = static_cast<uint8_t*>(const_cast<void*>(data));
+  p.scales = static_cast<uint8_t*>(const_cast<void*>(scales));
+  p.dps = dps; p.dts = dts; p.dhs = dhs;
+  p.sps = sps; p.sts = sts; p.shs = shs;
+  return p;
+}
+
+}  // namespace rx

@@ -172,6 +172,10 @@ PROTOTYPES = {
     "rx_decode_attn_mx4": (c_int, [C.POINTER(RxDecodeParams), C.POINTER(RxKvMx4Scales), c_void_p]),
     "rx_gather_kv_mx4": (c_int, [C.POINTER(RxKvLayout), C.POINTER(RxKvMx4Scales), c_void_p, c_int, c_int64, c_int, c_int,
                                  c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "rx_store_mla_mx4": (c_int, [c_void_p, c_void_p, C.POINTER(RxKvLayout), C.POINTER(RxKvMx4Scales), c_void_p, c_int64, c_int,
+                                 c_int, c_int64, c_int64, c_int, C.c_float, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "rx_gather_mla_mx4": (c_int, [C.POINTER(RxKvLayout), C.POINTER(RxKvMx4Scales), c_void_p, c_int, c_int64, c_int, c_int,
+                                  c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rx_extend_attn": (c_int, [C.POINTER(RxExtendParams), c_void_p]),
     "rx_alloc_extend": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "rx_alloc_decode": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),

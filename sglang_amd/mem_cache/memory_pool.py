@@ -403,3 +403,74 @@ class MLATokenToKVPool:
         if v:
             self.err_flag.zero_()
         return v
+
+
+class MLATokenToKVPoolFP4(MLATokenToKVPool):
+    """4-bit (MXFP4 block-16) latent rows: MLATokenToKVPoolFP4 (memory_pool.py:4182-4319) in the format of
+    FP4MXBlock16KVQuantizeUtil (include/radix_hip.h, "4-bit KV pool").  Per layer ``kv_buffer`` uint8 [size + page, 1,
+    (rank + rope) / 2] and ``kv_scale_buffer`` uint8 [size + page, (rank + rope) / 16] -- 324 B per token at 512 + 64
+    (1152 B in bf16).  ``dtype`` is the 16-bit dtype of the rows that come in and of the rows ``get_mla_kv_buffer`` hands
+    out.  Decode reads the packed bytes (rx_decode_attn_mx4 -> decode_mla_mx4_kernel); nothing ever dequantises a whole
+    layer, which is what the reference's get_key_buffer does on every call."""
+
+    def __init__(self, size: int, page_size: int, dtype: torch.dtype, kv_lora_rank: int,
+                 qk_rope_head_dim: int, layer_num: int, device: str, start_layer: int = 0):
+        if dtype not in (torch.bfloat16, torch.float16) or kv_lora_rank % 16 or qk_rope_head_dim % 16:
+            raise NotImplementedError("MLATokenToKVPoolFP4: a 16-bit row dtype, kv_lora_rank and qk_rope_head_dim multiples of 16")
+        self.is_fp8 = False
+        self.size, self.page_size, self.dtype, self.store_dtype = size, page_size, dtype, torch.uint8
+        self.kv_lora_rank, self.qk_rope_head_dim = kv_lora_rank, qk_rope_head_dim
+        self.kv_cache_dim = kv_lora_rank + qk_rope_head_dim
+        self.layer_num, self.device, self.start_layer = layer_num, device, start_layer
+        self.use_hnd = False
+        self.err_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        rows = size + page_size
+        self.kv_buffer = [torch.zeros((rows, 1, self.kv_cache_dim // 2), dtype=torch.uint8, device=device) for _ in range(layer_num)]
+        self.kv_scale_buffer = [torch.zeros((rows, self.kv_cache_dim // 16), dtype=torch.uint8, device=device) for _ in range(layer_num)]
+        bufs = self.kv_buffer + self.kv_scale_buffer  # data and scale rows travel together (move_kv_cache)
+        self.data_ptrs = torch.tensor([b.data_ptr() for b in bufs], dtype=torch.int64, device=device)
+        self.data_strides = torch.tensor([b.stride(0) for b in bufs], dtype=torch.int64, device=device)
+
+    def get_kv_size_bytes(self):
+        return sum(b.numel() for b in self.kv_buffer + self.kv_scale_buffer)
+
+    def get_key_buffer(self, layer_id: int):
+        raise NotImplementedError("MLATokenToKVPoolFP4 never dequantises a whole layer: attend the packed bytes "
+                                  "(get_mx4_buffers + ops.decode_attention_fwd(..., k_scale_buffer=)) or gather the rows a "
+                                  "batch needs (get_mla_kv_buffer / ops.get_mla_kv_mx4)")
+
+    get_value_buffer = get_key_buffer
+
+    def get_kv_buffer(self, layer_id: int):
+        return self.get_key_buffer(layer_id)
+
+    def get_mx4_buffers(self, layer_id: int):
+        """(data, scales) of a layer, packed bytes."""
+        li = layer_id - self.start_layer
+        return self.kv_buffer[li], self.kv_scale_buffer[li]
+
+    def get_contiguous_buf_infos(self):
+        bufs = self.kv_buffer + self.kv_scale_buffer
+        return [b.data_ptr() for b in bufs], [b.nbytes for b in bufs], [b[0].nbytes for b in bufs]
+
+    def _store(self, layer_id, loc, nope_or_row, rope):
+        if nope_or_row.dtype != self.dtype:
+            nope_or_row, rope = nope_or_row.to(self.dtype), None if rope is None else rope.to(self.dtype)
+        n = loc.shape[0]
+        ops.store_cache_mla_mx4(nope_or_row.reshape(n, -1), None if rope is None else rope.reshape(n, -1),
+                                *self.get_mx4_buffers(layer_id), loc, kv_lora_rank=self.kv_lora_rank,
+                                page_size=self.page_size, err_flag=self.err_flag)
+
+    def set_kv_buffer(self, layer, loc_info, cache_k: torch.Tensor, cache_v: torch.Tensor = None, *_, **__):
+        """memory_pool.py:4241-4270: the whole latent row comes in as cache_k; quantise and write, one launch."""
+        loc, _, _ = unwrap_write_loc(loc_info)
+        self._store(layer.layer_id, loc, cache_k, None)
+
+    def set_mla_kv_buffer(self, layer, loc: torch.Tensor, cache_k_nope: torch.Tensor, cache_k_rope: torch.Tensor):
+        """memory_pool.py:4272-4319: [nope | rope] from two tensors, one quantising launch."""
+        self._store(layer.layer_id, loc, cache_k_nope, cache_k_rope)
+
+    def get_mla_kv_buffer(self, layer, loc: torch.Tensor, dst_dtype: Optional[torch.dtype] = None):
+        """Dense 16-bit (nope [n, 1, rank], rope [n, 1, rope_dim]) of the rows at ``loc`` (exact): an extend's prefix."""
+        return ops.get_mla_kv_mx4(*self.get_mx4_buffers(layer.layer_id), loc, self.kv_lora_rank, self.qk_rope_head_dim,
+                                  dst_dtype or self.dtype, page_size=self.page_size, err_flag=self.err_flag)

@@ -204,11 +204,69 @@ def gather_kv_mx4(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, indices, d
 
 def _mx4_decode(p, q, k_buffer, v_buffer, k_scale_buffer, v_scale_buffer) -> None:
     """The decode call of a 4-bit pool (rx_decode_attn_mx4): p is filled as for rx_decode_attn, p.kv the data buffers."""
+    mla = _mx4_is_mla(k_buffer, p.head_dim, p.v_head_dim)
+    if mla:  # latent rows: ONE buffer, V = its first 512 columns (decode_mla_mx4_kernel)
+        if k_scale_buffer is None or v_scale_buffer not in (None, k_scale_buffer):
+            raise ValueError("4-bit latent pool: k_scale_buffer holds the rows' scale bytes; v_scale_buffer is None or the same tensor")
+        v_buffer, v_scale_buffer = k_buffer, k_scale_buffer
     lay, sc, hkv, dk, dv, _ = _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, p.kv.page_size)
-    if (dk, dv) != (p.head_dim, p.v_head_dim):
+    if (dk, dv) != (p.head_dim, p.v_head_dim) and not (mla and hkv == 1):
         raise ValueError(f"4-bit pool rows hold {dk} / {dv} elements, q / o {p.head_dim} / {p.v_head_dim}")
     p.kv, p.num_kv_heads = lay, hkv
     _L.check(_L.load().rx_decode_attn_mx4(C.byref(p), C.byref(sc), _stream(q)), "rx_decode_attn_mx4")
+
+
+def _mx4_is_mla(k_buffer, head_dim: int, v_head_dim: int) -> bool:
+    """4-bit latent rows (MLATokenToKVPoolFP4): 288 data bytes = 576 elements per row, attended by q 576 / o 512."""
+    return k_buffer.shape[-1] == 288 and (head_dim, v_head_dim) == (576, 512)
+
+
+def _mla_mx4_args(kv_buffer, kv_scale_buffer, page_size: int):
+    if kv_buffer.dim() not in (3, 4) or kv_buffer.shape[1] != 1:
+        raise ValueError("4-bit latent pool: data [slots, 1, D/2] (or [pages, 1, page, D/2]), scales [slots, D/16]")
+    lay, sc, _, d, _, slots = _mx4_pool_args(kv_buffer, kv_buffer, kv_scale_buffer, kv_scale_buffer, page_size)
+    return lay, sc, d, slots
+
+
+def store_cache_mla_mx4(nope_or_row, rope, kv_buffer, kv_scale_buffer, indices, *, kv_lora_rank: int = 512, page_size: int = 1,
+                        scale: float = 1.0, reserved_skip_index: int = 0, err_flag=None) -> None:
+    """Quantising store into a 4-bit latent pool (MLATokenToKVPoolFP4.set_kv_buffer / set_mla_kv_buffer,
+    srt/mem_cache/memory_pool.py:4241-4319): the whole [n, rank + rope] row (``rope`` None) or the [nope | rope] pair, one
+    launch (rx_store_mla_mx4).  Both widths are multiples of 16, so the pair quantises exactly as the concatenated row."""
+    _require_cuda(nope_or_row, rope, kv_buffer, kv_scale_buffer, indices)
+    a = nope_or_row.reshape(nope_or_row.shape[0], -1)
+    b = None if rope is None else rope.reshape(rope.shape[0], -1)
+    lay, sc, d, slots = _mla_mx4_args(kv_buffer, kv_scale_buffer, page_size)
+    if a.stride(-1) != 1 or (b is not None and (b.stride(-1) != 1 or b.dtype != a.dtype or b.shape[0] != a.shape[0])):
+        raise ValueError("store_cache_mla_mx4: sources share one 16-bit dtype and are contiguous in their last dim")
+    if a.shape[1] + (0 if b is None else b.shape[1]) != d or (b is not None and a.shape[1] != kv_lora_rank) or indices.numel() != a.shape[0]:
+        raise ValueError(f"store_cache_mla_mx4: source widths do not make the pool's {d}-wide row; one index per row")
+    idx = indices if indices.is_contiguous() else indices.contiguous()
+    st = _L.load().rx_store_mla_mx4(_ptr(a), _ptr(b), C.byref(lay), C.byref(sc), _ptr(idx), a.shape[0], kv_lora_rank,
+                                    d - kv_lora_rank, a.stride(0), 0 if b is None else b.stride(0), _rx_dtype(a), float(scale),
+                                    _is64(idx, "indices"), slots, reserved_skip_index, _ptr(err_flag), _stream(a))
+    _L.check(st, "rx_store_mla_mx4")
+
+
+def get_mla_kv_mx4(kv_buffer, kv_scale_buffer, loc, kv_lora_rank: int, rope_dim: int, dst_dtype: torch.dtype, *,
+                   page_size: int = 1, err_flag=None):
+    """The rows of a 4-bit latent pool at ``loc``, dequantised exactly into dense (nope [n, 1, rank], rope [n, 1, rope_dim])
+    of dst_dtype (rx_gather_mla_mx4): MLATokenToKVPoolFP4.get_mla_kv_buffer; what an extend over a 4-bit prefix attends."""
+    _require_cuda(kv_buffer, kv_scale_buffer, loc)
+    if dst_dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"get_mla_kv_mx4: dst_dtype {dst_dtype}")
+    lay, sc, d, slots = _mla_mx4_args(kv_buffer, kv_scale_buffer, page_size)
+    if kv_lora_rank + rope_dim != d:
+        raise ValueError(f"get_mla_kv_mx4: kv_lora_rank + rope_dim != the pool's {d}-wide row")
+    n = loc.numel()
+    nope = torch.empty((n, 1, kv_lora_rank), dtype=dst_dtype, device=kv_buffer.device)
+    rope = torch.empty((n, 1, rope_dim), dtype=dst_dtype, device=kv_buffer.device)
+    idx = loc if loc.is_contiguous() else loc.contiguous()
+    st = _L.load().rx_gather_mla_mx4(C.byref(lay), C.byref(sc), _ptr(idx), _is64(idx, "loc"), n, kv_lora_rank, rope_dim,
+                                     _ptr(nope), _ptr(rope), _L.RX_BF16 if dst_dtype == torch.bfloat16 else _L.RX_F16, slots,
+                                     _ptr(err_flag), _stream(kv_buffer))
+    _L.check(st, "rx_gather_mla_mx4")
+    return nope, rope
 
 
 def _mx4_reject(**given) -> None:
@@ -614,6 +672,8 @@ def decode_attention_fwd(q, k_buffer, v_buffer, o, kv_indptr, kv_indices, attn_l
     if mx4:
         _mx4_reject(score_mod=score_mod, stages=stages, merge_counters=merge_counters, k_new=k_new, v_new=v_new,
                     split_items=split_items)
+        if _mx4_is_mla(k_buffer, q.shape[-1], o.shape[-1]):
+            v_buffer = k_buffer  # (latent rows: V is the first 512 columns of the same bytes)
         kv_layout = kv_layout_hnd(k_buffer, v_buffer) if k_buffer.dim() == 4 else None  # (HND: the 4-D buffers say so)
     # has_mla only selects a Triton block shape in the reference; here the MLA kernel is chosen from the
     # tensor shapes (Dk 576 / Dv 512, one kv head, V aliasing K)
@@ -688,6 +748,9 @@ def decode_attention_fwd_grouped_rope(q, k_buffer, v_buffer, o, kv_indptr, kv_in
     Beyond the reference: ``k_new`` [bs, 576] -- the step's rows NOT stored yet: the launch reads them from k_new,
     rotates, attends and stores the finished rows (RoPE + KV store + attention in one launch); ``page_size`` /
     ``kv_layout`` for paged pools (the reference kernel is page_size 1 only).  16-bit pools, rotary_dim 64."""
+    if k_buffer.dtype == torch.uint8 and _mx4_is_mla(k_buffer, q.shape[-1], o.shape[-1]):
+        raise NotImplementedError("decode_attention_fwd_grouped_rope: fused RoPE is not supported on a 4-bit latent pool "
+                                  "(MLATokenToKVPoolFP4): rotate, store, then decode_attention_fwd(..., k_scale_buffer=)")
     _require_cuda(q, k_buffer, v_buffer, o, kv_indptr, kv_indices)
     if kv_lora_rank != 512 or q.shape[-1] != 576 or o.shape[-1] != 512:
         raise NotImplementedError("decode_attention_fwd_grouped_rope: the latent shape 512 + 64 only")
@@ -857,6 +920,8 @@ def decode_attention_fwd_paged(q, k_buffer, v_buffer, o, req_to_token, req_pool_
     if mx4:
         _mx4_reject(kv_start=kv_start, extra_o=extra_o, extra_lse=extra_lse, stages=stages, merge_counters=merge_counters,
                     k_new=k_new, v_new=v_new, split_items=split_items, score_mod=score_mod, units=units)
+        if _mx4_is_mla(k_buffer, q.shape[-1], o.shape[-1]):
+            v_buffer = k_buffer  # (latent rows: V is the first 512 columns of the same bytes)
         kv_layout = kv_layout_hnd(k_buffer, v_buffer) if k_buffer.dim() == 4 else None  # (HND: the 4-D buffers say so)
     p = _decode_paged_params(q, k_buffer, v_buffer, o, req_to_token, req_pool_indices, seq_lens, attn_logits, attn_lse,
                              num_kv_splits, max_kv_splits, sm_scale, k_scale, v_scale, logit_cap, sinks, page_size,
