@@ -454,9 +454,12 @@ int rx_decode_units(const int32_t* req_to_token, int64_t req_row_stride, const v
  *   ties go UP in magnitude, this is not round-to-nearest-even -- and the sign bit is s < 0.  With k_scale / v_scale
  *   != 1 the input is first divided and rounded to its own 16-bit dtype (the reference's in-place div_, as
  *   rx_store_kv_fp8).
- * Dequantised values are exact in bf16, and in fp16 while they are normal fp16 numbers (the quantiser fed fp16 inputs
- * never produces a value above 65504).  Blocks whose non-zero values fall below the call dtype's normal range, and the
- * scale bytes 0 and 255, are outside the contract.
+ * Dequantised values are exact in bf16, and in fp16 while they are normal fp16 numbers.  The top of the range is the one
+ * place where the quantiser leaves its input dtype: a block whose maximum is >= 3.5 * 2^(emax - 1) -- fp16 57344 .. 65504,
+ * bf16 3.5 * 2^126 and above -- gets scale byte emax + 126 (141 / 253) and code 6 or 7, which decode to 4 or 6 times
+ * 2^(emax - 1): above the largest finite number.  The gathers return the fp32 product rounded to the dtype there, inf, as
+ * the reference's dequantise does; attention over such a block is inf / NaN.  Blocks whose non-zero values fall below the
+ * call dtype's normal range, and the scale bytes 0 and 255, are outside the contract.
  * Layouts.  NHD, the reference's: data [slots, Hkv, D/2], scales [slots, Hkv * D/16].  HND pages: data [pages, Hkv,
  * page, D/2], scales [pages, Hkv, page, D/16].  The data buffers ride in rx_kv_layout as BYTE buffers with BYTE strides
  * (kv_fp8 is ignored by the entry points below); the scale buffers and their byte strides -- same addressing formula --
@@ -482,7 +485,8 @@ int rx_store_kv_mx4(const void* k, const void* v, const rx_kv_layout* lay /* HOS
  * layer per call -- followed by decode_attention_fwd).  p as for rx_decode_attn with p->kv the data buffers; head_dim ==
  * v_head_dim in {64, 128}; both lookup modes; sm_scale, k_scale, v_scale, logit_cap, sinks, xai_temperature_len,
  * request_order and the kv-split schedule (num_kv_splits / max_kv_splits with attn_logits / attn_lse, merged by the
- * stage-2 kernels of rx_decode_attn; max_kv_splits == 1 or num_kv_splits == NULL writes o directly) behave as there.
+ * stage-2 kernels of rx_decode_attn; max_kv_splits == 1 or num_kv_splits == NULL writes o directly, and so does a request
+ * with ONE split inside a split batch -- an empty request's rows are zero either way) behave as there.
  * RX_ERR_UNSUPPORTED: k_new / v_new, rope_cos_sin, score_bias, kv_start, extra partials, split_items, unit_desc,
  * merge_counters, stages != 0 and other head dims (latent rows 576 / 512: below).  Data rows must be D/8-byte aligned, scale rows
  * D/64-byte aligned.  rx_last_dispatch() names the decode_mx4_kernel instance. */

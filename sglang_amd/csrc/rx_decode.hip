@@ -1076,12 +1076,17 @@ extern "C" int rx_dev_decode_timeline(unsigned long long* out_host, int n) {
 }
 #endif
 
-static int decode_attn_impl(const rx_decode_params* p, void* stream);
+static int decode_attn_impl(const rx_decode_params* p, void* stream, bool stage2_direct_single = false);
 extern "C" int rx_decode_attn(const rx_decode_params* p, void* stream) {
   RX_RANGE("rx_decode_attn");
   return rx::dump_on_error("decode_attn", decode_attn_impl(p, stream), p, p ? sizeof(*p) : 0);
 }
-static int decode_attn_impl(const rx_decode_params* p, void* stream) {
+namespace rx {
+// stage 2 for a stage 1 of another file (rx_kv_mx4.hip) that keeps the direct_single rule: p->stages == 2, and the requests
+// with ONE kv split are left alone -- their stage 1 wrote the final output
+int decode_merge_partials(const rx_decode_params* p, void* stream) { return decode_attn_impl(p, stream, true); }
+}  // namespace rx
+static int decode_attn_impl(const rx_decode_params* p, void* stream, bool stage2_direct_single) {
   RX_REQUIRE(p, "rx_decode_attn: params is null");
   RX_REQUIRE(p->bs >= 0, "rx_decode_attn: bs < 0");
   if (p->bs == 0) return RX_OK;
@@ -1227,6 +1232,7 @@ static int decode_attn_impl(const rx_decode_params* p, void* stream) {
     RX_REQUIRE(p->num_kv_splits && p->max_kv_splits > 1, "rx_decode_attn: split_items go with a split schedule (num_kv_splits, max_kv_splits > 1)");
   }
   a.direct_single = ((mfma_ok || mla) && a.num_extra == 0 && max_splits > 1 && p->stages == 0) ? 1 : 0;
+  if (stage2_direct_single && p->stages == 2 && a.num_extra == 0) a.direct_single = 1;
   a.k_new = a.v_new = nullptr;
   if (mla) {
     // the latent kernel takes k_new (the whole new row, v is its prefix) only with fused RoPE: checked in launch_decode_mla

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256, 3) void decode_mla_mx4_kernel(const MlaMx4Args
     idx = reinterpret_cast<const IdxT*>(a.req_to_token + load_idx(a.req_pool_indices, b, a.rpi64) * a.req_row_stride);
   }
   const int32_t splits = (a.num_kv_splits && a.max_kv_splits > 1) ? a.num_kv_splits[b] : 1;
-  const bool single = a.max_kv_splits == 1;
+  const bool single = a.max_kv_splits == 1 || splits == 1;  // (direct_single: see decode_mx4_kernel)
   const int h = qb * 16 + r;
   const bool q_valid = h < a.hq;
   if (split >= splits) return;

@@ -197,7 +197,9 @@ __global__ __launch_bounds__(256, 2) void decode_mx4_kernel(const Mx4DecodeArgs 
     idx = reinterpret_cast<const IdxT*>(a.req_to_token + load_idx(a.req_pool_indices, b, a.rpi64) * a.req_row_stride);
   }
   const int32_t splits = (a.num_kv_splits && a.max_kv_splits > 1) ? a.num_kv_splits[b] : 1;
-  const bool single = a.max_kv_splits == 1;
+  // a request with ONE kv split writes its final output here and stage 2 leaves it alone (direct_single, rx_decode.hip):
+  // an empty request inside a split batch gets the zeros it gets from the 16-bit kernels
+  const bool single = a.max_kv_splits == 1 || splits == 1;
   const int gq = qb * 16 + r;  // q head inside the GQA group handled by this lane
   const bool q_valid = gq < a.group;
   const int h = kvh * a.group + gq;
@@ -510,6 +512,7 @@ extern "C" int rx_gather_kv_mx4(const rx_kv_layout* lay, const rx_kv_mx4_scales*
 
 namespace rx {
 int launch_decode_mla_mx4(const rx_decode_params* p, const rx_kv_mx4_scales* sc, int max_splits, hipStream_t s);  // rx_decode_mla_mx4.hip
+int decode_merge_partials(const rx_decode_params* p, void* stream);  // rx_decode.hip: stage 2, one-split requests left alone
 }
 
 // A one-tensor (latent) pool: the row [nope | rope] is ONE buffer of (rank + rope_dim) / 2 data bytes and (rank + rope_dim) / 16
@@ -687,7 +690,7 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
   m.request_order = nullptr;
   m.partial_pairs_hint = 0;
   m.stages = 2;
-  return rx_decode_attn(&m, stream);
+  return decode_merge_partials(&m, stream);
 }
 
 extern "C" int rx_decode_attn_mx4(const rx_decode_params* p, const rx_kv_mx4_scales* sc, void* stream) {

@@ -40,7 +40,7 @@ def _paged(rng, lens, page_size):
     return r2t, n_pages * page_size
 
 
-LEN_POOL = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 500, 777, 1025]
+LEN_POOL = [0, 1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 500, 777, 1025]
 
 
 @pytest.mark.parametrize("seed", range(12))
