@@ -1200,6 +1200,11 @@ static int decode_attn_impl(const rx_decode_params* p, void* stream, bool stage2
                    ((p->q_stride_t | p->q_stride_h | p->kv.k_tok_stride | p->kv.k_page_stride) % 8 == 0) &&
                    ((uintptr_t)p->q & 15) == 0 && ((uintptr_t)p->kv.k_buf & (p->kv.kv_fp8 ? 7 : 15)) == 0 &&
                    ((p->o_stride_t | p->o_stride_h) % 4 == 0) && ((uintptr_t)p->o & 7) == 0;
+  // (an fp8 latent pool has no other kernel to fall through to: say what the latent kernels need, not "head_dim 64/128")
+  if (!mla && dk == 576 && dv == 512 && p->kv.kv_fp8)
+    return fail(RX_ERR_INVALID_ARG, "rx_decode_attn: an fp8 latent pool (576 / 512) needs one kv head, v_buf == k_buf with equal strides, "
+                "q / pool strides that are multiples of 8 elements, 16-byte aligned q (pool: 8-byte), o strides that are multiples "
+                "of 4 elements and an 8-byte aligned o");
   // stage 2 inside the stage-1 kernel: the kernels that have the epilogue, both stages wanted, nothing else to merge,
   // and the vector stores of the merge possible
   const bool merge_in_kernel = p->merge_counters && p->stages == 0 && a.num_extra == 0 && max_splits > 1 &&

@@ -982,9 +982,9 @@ __device__ __forceinline__ void extend_mfma32_body(const Ext32Args a_in, unsigne
           for (int i = 0; i < NPASS; ++i) slot[i] = static_cast<int32_t>(idx_n[min(i * RPP + st_row, p_len_n - 1)]);
 #pragma unroll
           for (int i = 0; i < NPASS; ++i) {
-            const int64_t off = slot_off32<LINEAR>(slot[i], a.page_size, a.k_page_stride, a.k_tok_stride);
-            stg_k[i] = *reinterpret_cast<const u32x4*>(kb_n + off);
-            stg_v[i] = *reinterpret_cast<const u32x4*>(vb_n + off);
+            // (K and V each by their own strides: the two pools need not share a layout)
+            stg_k[i] = *reinterpret_cast<const u32x4*>(kb_n + slot_off32<LINEAR>(slot[i], a.page_size, a.k_page_stride, a.k_tok_stride));
+            stg_v[i] = *reinterpret_cast<const u32x4*>(vb_n + slot_off32<LINEAR>(slot[i], a.page_size, a.v_page_stride, a.v_tok_stride));
           }
         } else if (n_end_n > 0) {  // no prefix: tile 0 is the request's first new rows
           const uint16_t* ke_n = a.k_ext + qo0_n * a.k_stride_t + kvh_n * a.k_stride_h + 8 * st_chunk;
@@ -992,9 +992,8 @@ __device__ __forceinline__ void extend_mfma32_body(const Ext32Args a_in, unsigne
 #pragma unroll
           for (int i = 0; i < NPASS; ++i) {
             slot[i] = max(0, min(i * RPP + st_row, n_end_n - 1));
-            const int64_t off = mul_u32(slot[i], a.k_stride_t);
-            stg_k[i] = *reinterpret_cast<const u32x4*>(ke_n + off);
-            stg_v[i] = *reinterpret_cast<const u32x4*>(ve_n + off);
+            stg_k[i] = *reinterpret_cast<const u32x4*>(ke_n + mul_u32(slot[i], a.k_stride_t));
+            stg_v[i] = *reinterpret_cast<const u32x4*>(ve_n + mul_u32(slot[i], a.v_stride_t));  // (v may be a view of a fused qkv: its own stride)
           }
         }
         // (q rows last: the slot ids return first and tile 0's rows are requested without waiting for q)
