@@ -70,7 +70,8 @@ const char* rx_last_error(void);
  * rx_set_option, read once from RX_OPT_<NAME> at load -- the launch path itself never reads the environment.
  * Names: ext32_autopack, ext32_small_wg, ext32_plain, ext32_count_redo, extend_16x16_d128, extend_d256, extend_d256_at128,
  * extend_d256_at64, extend_d256_at96, extend_nd, extend_nd_big, extend_mla, extend_mla_shared_v, decode_mla8_dma, decode_mla8_t64,
- * merge_in_kernel_max_mb[_mla], ext32_uni (round 6), roctx; ar_fenced / qr_fenced (the all-reduce kernels' flag handshake
+ * merge_in_kernel_max_mb[_mla], ext32_uni (round 6), extend_mx4_native (read by the attention backend: an extend over a
+ * 4-bit pool through rx_extend_attn_mx4 -- -1, the default, by the shape rule of DESIGN 4.2c; 1 always; 0 never), roctx; ar_fenced / qr_fenced (the all-reduce kernels' flag handshake
  * in its fenced form), ar_spin_log2 (polls before a
  * flag wait gives up), ar_blocks (blocks of the decode-sized all-reduce kernels; 0 = by message size), qr_max_blocks (the quick all-reduce's grid cap); ext64 only acts in a dev build (RX_WITH_EXT64=1).
  * NOT THREAD-SAFE: the switches are plain process-wide ints that the launch path reads without synchronisation.  Set them
@@ -621,6 +622,20 @@ typedef struct rx_extend_params {
 } rx_extend_params;
 
 int rx_extend_attn(const rx_extend_params* p /* HOST */, void* stream);
+
+/* Extend attention over the 4-bit pool: the cached prefix read as packed nibbles + scale bytes, the new tokens' K / V as
+ * the 16-bit k_extend / v_extend rows, in ONE pass (rx::extend_mx4_kernel, rx_extend_mx4.hip) -- in place of
+ * rx_gather_kv_mx4 + rx_extend_attn on the dense copy, with the same result bound (the unpack is exact, the output is
+ * rounded once).  p as for rx_extend_attn with p->kv the DATA buffers as byte buffers with byte strides, scales beside it;
+ * head_dim == v_head_dim in {64, 128}, both dtypes, any Hq / Hkv, kv_indices / qo_indptr in either width, linear / NHD /
+ * HND pools, is_causal, sm_scale, k_scale / v_scale (on the cached part, as rx_extend_attn applies them), logit_cap, lse,
+ * skip_extend (the keys are the prefix only and every query sees all of it), empty prefixes.  A row with no visible key
+ * gets zeros and lse = -inf.  skip_prefix: the call is rx_extend_attn's and is forwarded to it.
+ * RX_ERR_UNSUPPORTED (the message names the field): custom_mask, sliding_window_size, sinks, xai_temperature_len,
+ * score_bias, unified_prefix_lens, q_pack > 1 (the kernel packs (token, q head) rows by itself), window_kv_offsets, other
+ * head dims, latent rows 576 / 512, data rows not D/8-byte or scale rows not D/64-byte aligned, q / k / v / o strides that
+ * are not multiples of 8 elements.  rx_last_dispatch() names "extend_mx4_kernel<rx::BF16, 128, long, false>|g4". */
+int rx_extend_attn_mx4(const rx_extend_params* p /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, void* stream);
 
 /* ---- fused rotary embedding + KV store ---------------------------------------------------------
  * q [n, Hq, D] and k [n, Hkv, D] are rotated IN PLACE (positions int64[n], cos_sin_cache fp32

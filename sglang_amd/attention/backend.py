@@ -35,6 +35,17 @@ from .. import ops
 from ..forward_batch import ForwardBatch
 from ..mem_cache import memory_pool as _own_pools
 
+MX4_NATIVE_MAX_ROWS = 64
+
+
+def mx4_extend_native_rule(max_extend_len: int, group: int, n_req: int, num_kv_heads: int, cus: int) -> bool:
+    """Option extend_mx4_native = -1 (the default): an extend over a 4-bit pool reads the packed prefix natively iff the
+    longest request's new tokens x G q heads fit ONE 64-row block of extend_mx4_kernel (max_extend_len * G <= 64) AND its
+    grid, one workgroup per (request, kv head), is at least half the CU count.  Measured: 0.37-0.71x the
+    gather route from 128 workgroups up over prefixes of 256 .. 32 k; 1.2-2.4x at 64 and 8 workgroups (a workgroup walks
+    its prefix at ~2.6 us per tile whatever the grid), 1.15-2.4x at 256 rows and more."""
+    return max_extend_len * group <= MX4_NATIVE_MAX_ROWS and 2 * n_req * num_kv_heads >= cus
+
 
 def draft_kv_indices_buffer_width(num_seqs: int, topk: int, max_context_len: int) -> int:
     """Row width of the multi-step draft kv_indices buffer (srt/speculative/spec_utils.py:181-192)."""
@@ -352,6 +363,7 @@ class HipRadixAttnBackend:
     def _build_metadata(self, forward_batch: ForwardBatch, graph: bool):
         from .. import lib as _lib
         self._roctx = bool(_lib.get_option("roctx"))
+        self._mx4_native_opt = _lib.get_option("extend_mx4_native") if self._is_mx4_pool else 0
         bs = forward_batch.batch_size
         mode = forward_batch.forward_mode
         self._md_version += 1
@@ -1280,6 +1292,16 @@ class HipRadixAttnBackend:
             # 16-bit extend runs on it; the new tokens' own K / V stay 16-bit, as in the reference
             if score_mod is not None:
                 raise NotImplementedError("score_mod is not supported on a 4-bit (MXFP4) KV pool")
+            if self._mx4_extend_is_native(layer, md, sinks):
+                # the packed prefix and the new tokens' 16-bit rows in one pass (rx_extend_attn_mx4): no dense copy
+                kb, vb, ksb, vsb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
+                ops.extend_attention_fwd(
+                    q.view(-1, layer.tp_q_head_num, layer.qk_head_dim), k.view(-1, layer.tp_k_head_num, layer.qk_head_dim),
+                    v.view(-1, layer.tp_v_head_num, layer.v_head_dim), o.view(-1, layer.tp_q_head_num, layer.v_head_dim),
+                    kb, vb, md.qo_indptr, md.kv_indptr, md.kv_indices, None, causal, None, md.max_extend_len, k_descale,
+                    v_descale, sm_scale=layer.scaling, logit_cap=layer.logit_cap, page_size=self.page_size,
+                    k_scale_buffer=ksb, v_scale_buffer=vsb)
+                return o
             n_pre = int(sum(forward_batch.extend_prefix_lens_cpu)) if forward_batch.extend_prefix_lens_cpu is not None else None
             idx = md.kv_indices if n_pre is None else md.kv_indices[:n_pre]
             if idx.numel() == 0:  # no prefix anywhere: nothing is read from the pool
@@ -1358,6 +1380,19 @@ class HipRadixAttnBackend:
             xai_temperature_len=layer.xai_temperature_len, page_size=page_size, kv_layout=lay,
             score_mod=score_mod, aux_tensors=aux_tensors)
         return o
+
+    def _mx4_extend_is_native(self, layer, md, sinks) -> bool:
+        """An extend over MHATokenToKVPoolFP4 reads the packed prefix natively when the call uses nothing rx_extend_attn_mx4
+        refuses (tree masks, sinks, the Grok temperature, latent rows, other head dims) and option ``extend_mx4_native`` (read
+        with the forward's metadata) says so: 1 always, 0 never, -1 by mx4_extend_native_rule."""
+        if (self._is_mla_mx4_pool or md.custom_mask is not None or sinks is not None or md.max_extend_len is None
+                or (getattr(layer, "xai_temperature_len", -1) or 0) > 0
+                or layer.qk_head_dim != layer.v_head_dim or layer.qk_head_dim not in (64, 128)):
+            return False
+        if self._mx4_native_opt >= 0:
+            return bool(self._mx4_native_opt)
+        return mx4_extend_native_rule(md.max_extend_len, layer.tp_q_head_num // layer.tp_k_head_num, md.qo_indptr.shape[0] - 1,
+                                      layer.tp_k_head_num, self.device_core_count)
 
     def _forward_extend_unified(self, q, o, layer, forward_batch: ForwardBatch, causal: bool, sinks, score_mod=None,
                                 aux_tensors=None):

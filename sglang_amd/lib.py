@@ -177,6 +177,7 @@ PROTOTYPES = {
     "rx_gather_mla_mx4": (c_int, [C.POINTER(RxKvLayout), C.POINTER(RxKvMx4Scales), c_void_p, c_int, c_int64, c_int, c_int,
                                   c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rx_extend_attn": (c_int, [C.POINTER(RxExtendParams), c_void_p]),
+    "rx_extend_attn_mx4": (c_int, [C.POINTER(RxExtendParams), C.POINTER(RxKvMx4Scales), c_void_p]),
     "rx_alloc_extend": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "rx_alloc_decode": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
     "rx_write_req_to_token": (c_int, [c_void_p, c_int64] + [c_void_p] * 6 + [c_int, c_void_p]),

@@ -1613,7 +1613,26 @@ def extend_attention_fwd(q_extend, k_extend, v_extend, o_extend, k_buffer, v_buf
                          window_kv_offsets=None, xai_temperature_len=-1, lse_extend=None,
                          skip_prefix=False, skip_extend=False, page_size: int = 1,
                          score_mod=None, aux_tensors=None, kv_layout=None, unified_prefix_lens=None,
-                         _num_kv_heads=None, avg_kv_len_hint=None, q_pack: int = 1):
+                         _num_kv_heads=None, avg_kv_len_hint=None, q_pack: int = 1,
+                         k_scale_buffer=None, v_scale_buffer=None):
+    """``k_scale_buffer`` / ``v_scale_buffer``: k_buffer / v_buffer are the data bytes of a 4-bit (MXFP4 block-16) pool and
+    these its scale bytes; the prefix is read packed (rx_extend_attn_mx4, one pass with the new tokens' 16-bit rows).  Masks,
+    windows, sinks, the Grok temperature, score_mod, the unified form and q_pack raise NotImplementedError there."""
+    mx4 = k_scale_buffer is not None or v_scale_buffer is not None
+    sc = None
+    if mx4:
+        _mx4_reject(custom_mask=custom_mask, sliding_window_size=sliding_window_size if (sliding_window_size or 0) > 0 else None,
+                    sinks=sinks, xai_temperature_len=xai_temperature_len if (xai_temperature_len or 0) > 0 else None,
+                    score_mod=score_mod, unified_prefix_lens=unified_prefix_lens, q_pack=q_pack if q_pack > 1 else None,
+                    window_kv_offsets=window_kv_offsets)
+        if k_scale_buffer is None or v_scale_buffer is None:
+            raise ValueError("4-bit pool: k_scale_buffer and v_scale_buffer are given together")
+        _require_cuda(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer)
+        kv_layout, sc, hkv, dk, dv, _ = _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size)
+        if hkv != (k_extend.shape[1] if _num_kv_heads is None else int(_num_kv_heads)):
+            raise ValueError(f"4-bit pool rows hold {hkv} kv heads, the call {k_extend.shape[1]}")
+        if (dk, dv) != (q_extend.shape[-1], o_extend.shape[-1]):
+            raise ValueError(f"4-bit pool rows hold {dk} / {dv} elements, q / o {q_extend.shape[-1]} / {o_extend.shape[-1]}")
     p = _extend_params(q_extend, k_extend, v_extend, o_extend, k_buffer, v_buffer, qo_indptr, kv_indptr, kv_indices,
                        custom_mask, is_causal, mask_indptr, max_len_extend, k_scale, v_scale, sm_scale=sm_scale,
                        logit_cap=logit_cap, skip_prefix_custom_mask=skip_prefix_custom_mask,
@@ -1622,6 +1641,8 @@ def extend_attention_fwd(q_extend, k_extend, v_extend, o_extend, k_buffer, v_buf
                        skip_extend=skip_extend, page_size=page_size, score_mod=score_mod, aux_tensors=aux_tensors,
                        kv_layout=kv_layout, unified_prefix_lens=unified_prefix_lens, _num_kv_heads=_num_kv_heads,
                        avg_kv_len_hint=avg_kv_len_hint, q_pack=q_pack)
+    if mx4:
+        return _L.check(_L.load().rx_extend_attn_mx4(C.byref(p), C.byref(sc), _stream(q_extend)), "rx_extend_attn_mx4")
     _L.check(_L.load().rx_extend_attn(C.byref(p), _stream(q_extend)), "rx_extend_attn")
 
 
