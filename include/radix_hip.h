@@ -221,7 +221,15 @@ int rx_split_items_guarded(int32_t* num_kv_splits, const int32_t* order, int bs,
  *     tok_stride = Hkv*D, head_stride = D.
  * HND [pages, Hkv, page, D] (memory_pool.py:2032-2036): page_stride = Hkv*page*D,
  *     tok_stride = D, head_stride = page*D.
- * (mirrors _extract_kv_strides, kernels/ops/attention/decode_attention.py:39-88) */
+ * (mirrors _extract_kv_strides, kernels/ops/attention/decode_attention.py:39-88)
+ * Bounds.  The offset is a 64-bit sum of 64-bit products: a pool may hold far more than 2^32 elements (or bytes).  Its
+ * factors are not: the attention kernels multiply with 32-bit operands, so page_stride and tok_stride must lie in
+ * [0, 2^31) -- rx_decode_attn, rx_extend_attn and their _mx4 forms return RX_ERR_INVALID_ARG otherwise, before any
+ * launch -- and slot ids in [0, 2^31) (an int32 req_to_token table cannot say more; an int64 kv_indices entry beyond
+ * that is outside the contract and not checked: the ids live on the device).  The stores, gathers and moves
+ * (rx_store_kv*, rx_store_mla_mx4, rx_fused_fp8_qkv_kv_cache, rx_rope_store_kv, rx_qknorm_rope_store_kv, rx_get_mla_kv,
+ * rx_gather_*_mx4, rx_move_kv*) compute in 64 bits throughout and have no such bound (tests/test_gpu_big_pool.py runs
+ * each of them, and every attention family, above 2^32 elements). */
 typedef struct rx_kv_layout {
   const void* k_buf;
   const void* v_buf;
@@ -464,7 +472,8 @@ int rx_decode_units(const int32_t* req_to_token, int64_t req_row_stride, const v
  * Layouts.  NHD, the reference's: data [slots, Hkv, D/2], scales [slots, Hkv * D/16].  HND pages: data [pages, Hkv,
  * page, D/2], scales [pages, Hkv, page, D/16].  The data buffers ride in rx_kv_layout as BYTE buffers with BYTE strides
  * (kv_fp8 is ignored by the entry points below); the scale buffers and their byte strides -- same addressing formula --
- * ride in rx_kv_mx4_scales beside it. */
+ * ride in rx_kv_mx4_scales beside it, under rx_kv_layout's bounds: page and token strides in [0, 2^31) bytes for
+ * rx_decode_attn_mx4 / rx_extend_attn_mx4 (RX_ERR_INVALID_ARG otherwise). */
 typedef struct rx_kv_mx4_scales {
   const void* k_scale_buf;
   const void* v_scale_buf;
@@ -563,7 +572,7 @@ typedef struct rx_extend_params {
   const void* v_extend; /* [T, Hkv, Dv] */
   void* o;              /* [T, Hq, Dv] */
   int64_t q_stride_t, q_stride_h, k_stride_t, k_stride_h, v_stride_t, v_stride_h, o_stride_t,
-      o_stride_h;
+      o_stride_h; /* k_stride_t / v_stride_t in [0, 2^31), as rx_kv_layout's strides (RX_ERR_INVALID_ARG otherwise) */
   rx_kv_layout kv;
   const void* qo_indptr; /* [bs+1] */
   int32_t qo_indptr_is_i64;

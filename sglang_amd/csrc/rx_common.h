@@ -207,6 +207,20 @@ __device__ __forceinline__ int64_t mul_u32(int64_t slot, int64_t stride) {
   return static_cast<int64_t>(static_cast<uint64_t>(static_cast<uint32_t>(slot)) *
                               static_cast<uint32_t>(stride));
 }
+// The host side of that assumption: the attention entry points refuse (RX_ERR_INVALID_ARG) a per-page or per-token
+// stride outside [0, 2^31) before they launch.  The bound also covers the LDS pointer tables of rx_extend_d256.hip and
+// rx_extend_mla.hip, which hold 2 * stride (the byte stride of 16-bit rows) in 32 bits.  The product itself is 64-bit:
+// a pool may be far larger than 2^32 elements.  (Slot ids live on the device: they are < 2^31 by the int32
+// req_to_token table, and an int64 kv_indices entry beyond that is outside the contract.)
+inline bool stride_fits_u31(int64_t s) { return s >= 0 && s < (int64_t{1} << 31); }
+inline bool kv_strides_fit_u31(const rx_kv_layout& kv) {
+  return stride_fits_u31(kv.k_page_stride) && stride_fits_u31(kv.k_tok_stride) && stride_fits_u31(kv.v_page_stride) &&
+         stride_fits_u31(kv.v_tok_stride);
+}
+inline bool kv_strides_fit_u31(const rx_kv_mx4_scales& sc) {
+  return stride_fits_u31(sc.k_page_stride) && stride_fits_u31(sc.k_tok_stride) && stride_fits_u31(sc.v_page_stride) &&
+         stride_fits_u31(sc.v_tok_stride);
+}
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 

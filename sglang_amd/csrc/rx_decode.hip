@@ -1090,6 +1090,8 @@ static int decode_attn_impl(const rx_decode_params* p, void* stream, bool stage2
   RX_REQUIRE(p, "rx_decode_attn: params is null");
   RX_REQUIRE(p->bs >= 0, "rx_decode_attn: bs < 0");
   if (p->bs == 0) return RX_OK;
+  RX_REQUIRE(kv_strides_fit_u31(p->kv),
+             "rx_decode_attn: per-page / per-token strides of the pool must lie in [0, 2^31) elements");
   RX_REQUIRE(p->q && p->o && p->kv.k_buf && p->kv.v_buf, "rx_decode_attn: null q/o/k_buf/v_buf");
   RX_REQUIRE(p->num_q_heads > 0 && p->num_kv_heads > 0 && p->num_q_heads % p->num_kv_heads == 0,
              "rx_decode_attn: Hq=%d must be a positive multiple of Hkv=%d", p->num_q_heads,

@@ -628,6 +628,11 @@ static int extend_attn_impl(const rx_extend_params* p, void* stream) {
   RX_REQUIRE(p, "rx_extend_attn: params is null");
   RX_REQUIRE(p->bs >= 0 && p->max_extend_len >= 0, "rx_extend_attn: negative sizes");
   if (p->bs == 0 || p->max_extend_len == 0) return RX_OK;
+  // (the unified form reads no k_extend / v_extend: their strides are not looked at)
+  RX_REQUIRE(kv_strides_fit_u31(p->kv) &&
+                 (p->unified_prefix_lens || (stride_fits_u31(p->k_stride_t) && stride_fits_u31(p->v_stride_t))),
+             "rx_extend_attn: per-page / per-token strides of the pool and of k_extend / v_extend must lie in "
+             "[0, 2^31) elements");
   RX_REQUIRE(p->q && p->o, "rx_extend_attn: null q/o");
   RX_REQUIRE(p->unified_prefix_lens || (p->k_extend && p->v_extend), "rx_extend_attn: null k_extend/v_extend");
   if (p->unified_prefix_lens)

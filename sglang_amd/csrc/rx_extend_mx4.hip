@@ -342,6 +342,10 @@ static int extend_attn_mx4_impl(const rx_extend_params* p, const rx_kv_mx4_scale
   }
   RX_REQUIRE(p->bs >= 0 && p->max_extend_len >= 0, "rx_extend_attn_mx4: negative sizes");
   if (p->bs == 0 || p->max_extend_len == 0) return RX_OK;
+  RX_REQUIRE(kv_strides_fit_u31(p->kv) && kv_strides_fit_u31(*sc) &&
+                 (p->skip_extend || (stride_fits_u31(p->k_stride_t) && stride_fits_u31(p->v_stride_t))),
+             "rx_extend_attn_mx4: per-page / per-token strides of the data and scale buffers (bytes) and of "
+             "k_extend / v_extend (elements) must lie in [0, 2^31)");
   RX_REQUIRE(p->q && p->o, "rx_extend_attn_mx4: null q / o");
   RX_REQUIRE(p->skip_extend || (p->k_extend && p->v_extend), "rx_extend_attn_mx4: null k_extend / v_extend");
   RX_REQUIRE(p->qo_indptr && p->kv_indptr && p->kv_indices, "rx_extend_attn_mx4: null qo_indptr / kv_indptr / kv_indices");

@@ -586,6 +586,8 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
   RX_REQUIRE(sc, "rx_decode_attn_mx4: scales is null");
   RX_REQUIRE(p->bs >= 0, "rx_decode_attn_mx4: bs < 0");
   if (p->bs == 0) return RX_OK;
+  RX_REQUIRE(kv_strides_fit_u31(p->kv) && kv_strides_fit_u31(*sc),
+             "rx_decode_attn_mx4: per-page / per-token byte strides of the data and scale buffers must lie in [0, 2^31)");
   RX_REQUIRE(p->q && p->o, "rx_decode_attn_mx4: null q / o");
   RX_REQUIRE(p->num_q_heads > 0 && p->num_kv_heads > 0 && p->num_q_heads % p->num_kv_heads == 0,
              "rx_decode_attn_mx4: Hq=%d must be a positive multiple of Hkv=%d", p->num_q_heads, p->num_kv_heads);
