@@ -1082,6 +1082,16 @@ class HipRadixAttnBackend:
             return layer.k_scale_float, layer.v_scale_float
         return 1.0, 1.0
 
+    def _store_scales(self, layer):
+        """(k_scale, v_scale) as the decode step's set_kv_buffer gets them.  A loaded model keeps them as device tensors
+        (k_scale / v_scale) next to the floats it cached at load time (k_scale_float); OUR pools want plain floats, and float() of
+        a device tensor is a host sync -- refused inside a graph capture, where every decode step's store runs.  So our
+        pools get the cached floats; a foreign pool gets the layer's own objects, as the reference hands them over."""
+        if self._own_pool and layer.k_scale is not None and layer.v_scale is not None and layer.k_scale_float is not None \
+                and layer.v_scale_float is not None:
+            return layer.k_scale_float, layer.v_scale_float
+        return layer.k_scale, layer.v_scale
+
     def _fused_store_ok(self, layer, k, v) -> bool:
         """rx_decode_params.k_new: the new token's rows are read from k / v and written to their slots by the decode
         kernel itself -- one of OUR pools (or a foreign one that declares ``supports_fused_decode_store``: the fused
@@ -1131,7 +1141,7 @@ class HipRadixAttnBackend:
                 self._dcp_store(layer, forward_batch, k, v)
             else:
                 self.token_to_kv_pool.set_kv_buffer(layer, self._loc_info(forward_batch.out_cache_loc), k, v,
-                                                    layer.k_scale, layer.v_scale)
+                                                    *self._store_scales(layer))
         md = self.forward_metadata
         q3 = q.view(-1, layer.tp_q_head_num, layer.qk_head_dim)
         o3 = o.view(-1, layer.tp_q_head_num, layer.v_head_dim)

@@ -869,17 +869,7 @@ def test_short_mla_extend_over_long_prefix_takes_split_kv_path():
     parity.check_out(got, want, o.dtype, "short mla extend, split-KV path", ulps=2, absw=absw)  # (16-bit chunk partials: 2 ulp)
 
 
-def _capture(fn):
-    """Warm on a side stream (allocator, lazy launchers), then capture fn() into a HIP graph."""
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = fn()
-    return graph, out
+from graph_replay_util import capture as _capture  # noqa: E402  (warm on a side stream, then capture into a HIP graph)
 
 
 @pytest.mark.parametrize("index_mode,policy", [("paged", "native"), ("indices", "native"), ("paged", "reference"),
