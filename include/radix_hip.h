@@ -71,7 +71,8 @@ const char* rx_last_error(void);
  * Names: ext32_autopack, ext32_small_wg, ext32_plain, ext32_count_redo, extend_16x16_d128, extend_d256, extend_d256_at128,
  * extend_d256_at64, extend_d256_at96, extend_nd, extend_nd_big, extend_mla, extend_mla_shared_v, decode_mla8_dma, decode_mla8_t64,
  * merge_in_kernel_max_mb[_mla], ext32_uni (round 6), extend_mx4_native (read by the attention backend: an extend over a
- * 4-bit pool through rx_extend_attn_mx4 -- -1, the default, by the shape rule of DESIGN 4.2c; 1 always; 0 never), roctx; ar_fenced / qr_fenced (the all-reduce kernels' flag handshake
+ * 4-bit pool through rx_extend_attn_mx4 -- -1, the default, by the shape rule of DESIGN 4.2c; 1 always; 0 never), cascade_mx4 (1: rx_extend_attn_mx4's
+ * skip_extend, not-causal form on cascade_mx4_kernel; 0, the default the measurement of DESIGN 4.1c supports: on extend_mx4_kernel), roctx; ar_fenced / qr_fenced (the all-reduce kernels' flag handshake
  * in its fenced form), ar_spin_log2 (polls before a
  * flag wait gives up), ar_blocks (blocks of the decode-sized all-reduce kernels; 0 = by message size), qr_max_blocks (the quick all-reduce's grid cap); ext64 only acts in a dev build (RX_WITH_EXT64=1).
  * NOT THREAD-SAFE: the switches are plain process-wide ints that the launch path reads without synchronisation.  Set them
@@ -497,8 +498,13 @@ int rx_store_kv_mx4(const void* k, const void* v, const rx_kv_layout* lay /* HOS
  * request_order and the kv-split schedule (num_kv_splits / max_kv_splits with attn_logits / attn_lse, merged by the
  * stage-2 kernels of rx_decode_attn; max_kv_splits == 1 or num_kv_splits == NULL writes o directly, and so does a request
  * with ONE split inside a split batch -- an empty request's rows are zero either way) behave as there.
- * RX_ERR_UNSUPPORTED: k_new / v_new, rope_cos_sin, score_bias, kv_start, extra partials, split_items, unit_desc,
- * merge_counters, stages != 0 and other head dims (latent rows 576 / 512: below).  Data rows must be D/8-byte aligned, scale rows
+ * Shared-prefix decode: kv_start in the req_to_token lookup (request b attends [kv_start[b], seq_len_b)) and the extra
+ * partials (extra_o / extra_lse / num_extra_partials / extra_index, which need max_kv_splits > 1): with extras EVERY request
+ * writes its partials and stage 2 merges them with the extras -- also a request with one split or an empty suffix; sinks
+ * join once, there.
+ * RX_ERR_UNSUPPORTED: k_new / v_new, rope_cos_sin, score_bias, kv_start with kv_indices, xai_temperature_len with kv_start,
+ * split_items, unit_desc, merge_counters, stages != 0, latent rows with kv_start / extra partials
+ * and other head dims (latent rows 576 / 512: below).  Data rows must be D/8-byte aligned, scale rows
  * D/64-byte aligned.  rx_last_dispatch() names the decode_mx4_kernel instance. */
 int rx_decode_attn_mx4(const rx_decode_params* p /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, void* stream);
 
@@ -643,7 +649,10 @@ int rx_extend_attn(const rx_extend_params* p /* HOST */, void* stream);
  * RX_ERR_UNSUPPORTED (the message names the field): custom_mask, sliding_window_size, sinks, xai_temperature_len,
  * score_bias, unified_prefix_lens, q_pack > 1 (the kernel packs (token, q head) rows by itself), window_kv_offsets, other
  * head dims, latent rows 576 / 512, data rows not D/8-byte or scale rows not D/64-byte aligned, q / k / v / o strides that
- * are not multiples of 8 elements.  rx_last_dispatch() names "extend_mx4_kernel<rx::BF16, 128, long, false>|g4". */
+ * are not multiples of 8 elements.  rx_last_dispatch() names "extend_mx4_kernel<rx::BF16, 128, long, false>|g4".
+ * skip_extend && !is_causal is phase 1 of shared-prefix decode (every row sees the whole chunk, many rows): with option
+ * cascade_mx4 = 1 it runs rx::cascade_mx4_kernel (rx_cascade_mx4.hip; 128 packed rows per workgroup,
+ * "cascade_mx4_kernel<...>|g4"); the default 0 keeps it on extend_mx4_kernel, which measured faster. */
 int rx_extend_attn_mx4(const rx_extend_params* p /* HOST */, const rx_kv_mx4_scales* scales /* HOST */, void* stream);
 
 /* ---- fused rotary embedding + KV store ---------------------------------------------------------

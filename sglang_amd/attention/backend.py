@@ -236,11 +236,14 @@ class HipRadixAttnBackend:
         if self.split_tile_size is not None:
             self.max_kv_splits = (self.max_context_len + self.split_tile_size - 1) // self.split_tile_size
         self.split_policy = split_policy
-        if self._is_mx4_pool and (cascade_decode or self.enable_deterministic or dcp is not None
+        # (cascade_decode: the MHA pool at head dims 128 / 64 -- rx::cascade_mx4_kernel + rx_decode_attn_mx4's kv_start / extras)
+        mx4_cascade_ok = (not self._is_mla_mx4_pool and self._is_mx4_pool and self.v_head_dim in (64, 128)
+                          and getattr(self.token_to_kv_pool, "head_dim", None) == self.v_head_dim)
+        if self._is_mx4_pool and ((cascade_decode and not mx4_cascade_ok) or self.enable_deterministic or dcp is not None
                                   or getattr(model_runner, "sliding_window_size", None)):
             raise NotImplementedError(f"a 4-bit (MXFP4) KV pool ({type(self.token_to_kv_pool).__name__}) serves the plain "
-                                      "decode / extend paths: no cascade_decode, deterministic inference, DCP or "
-                                      "sliding-window layers")
+                                      "decode / extend paths and, for MHA rows of head dim 128 / 64, cascade_decode: no "
+                                      "cascade_decode on latent rows, no deterministic inference, DCP or sliding-window layers")
         self.native_split_cap = 32
         # graph replay: upper bound of the fp32 kv-split partials [bs, Hq, slots, Dv] kept address-stable (bytes)
         self.graph_partials_budget = int(getattr(sa, "rx_graph_partials_budget", 256 << 20) or (256 << 20))
@@ -465,6 +468,8 @@ class HipRadixAttnBackend:
         return groups
 
     def _kv_head_dim_ok_for_groups(self) -> bool:
+        if self._is_mx4_pool:  # (accepted at construction only for MHA rows of head dim 128 / 64; get_key_buffer raises there)
+            return True
         kb = self.token_to_kv_pool.get_key_buffer(getattr(self.token_to_kv_pool, "start_layer", 0))
         return (kb.shape[-1] in (64, 96, 128, 256) and kb.shape[-1] == self.v_head_dim
                 and kb.dtype in (torch.bfloat16, torch.float16))
@@ -520,12 +525,17 @@ class HipRadixAttnBackend:
         if groups:
             # several shared prefixes (one per radix-tree node), or one that only part of the batch shares
             if self._cascade_groups is None:
-                kb = self.token_to_kv_pool.get_key_buffer(getattr(self.token_to_kv_pool, "start_layer", 0))
+                pool = self.token_to_kv_pool
+                if self._is_mx4_pool:  # (no 16-bit view of the packed rows: the pool's head dim and row dtype)
+                    d, qdt = pool.head_dim, pool.dtype
+                else:
+                    kb = pool.get_key_buffer(getattr(pool, "start_layer", 0))
+                    d, qdt = kb.shape[-1], self._q_dtype(kb)
                 try:
                     self._cascade_groups = ops.CascadeGroups(
-                        self.req_to_token_pool.size, self.num_head, self.num_kv_head, kb.shape[-1], self._q_dtype(kb),
+                        self.req_to_token_pool.size, self.num_head, self.num_kv_head, d, qdt,
                         self.device, max_shared_total=max(self.req_to_token.shape[1], self.cascade_groups_max_shared),
-                        cu_count=self.device_core_count, max_kv_splits=self.native_split_cap)
+                        cu_count=self.device_core_count, max_kv_splits=self.native_split_cap, mx4=self._is_mx4_pool)
                 except torch.OutOfMemoryError:
                     # created on the first grouped step, after the KV pool took its share of the memory: without room
                     # for the gathered queries / partials the batch takes the plain path (same results)
@@ -535,6 +545,12 @@ class HipRadixAttnBackend:
                 self._cascade_on, self._cascade_call = True, self._cascade_groups
                 return ForwardMetadata(None, None, None, None, None, None, None, 1)
         if self._cascade_on:
+            if self._cascade is None and self._is_mx4_pool:
+                pool = self.token_to_kv_pool
+                self._cascade = ops.CascadeDecode(
+                    self.req_to_token_pool.size, self.num_head, self.num_kv_head, pool.head_dim, pool.dtype, self.device,
+                    max_shared=self.req_to_token.shape[1], cu_count=self.device_core_count,
+                    min_shared=self.cascade_min_shared, max_kv_splits=self.native_split_cap, mx4=True)
             if self._cascade is None:
                 kb = self.token_to_kv_pool.get_key_buffer(getattr(self.token_to_kv_pool, "start_layer", 0))
                 mla = (self._is_mla_pool and kb.shape[-1] == 576 and self.v_head_dim == 512
@@ -1247,6 +1263,13 @@ class HipRadixAttnBackend:
         if md.draft or (layer.sliding_window_size is not None and layer.sliding_window_size > -1):
             raise NotImplementedError(f"draft decode / sliding-window layers are not supported on a 4-bit (MXFP4) KV pool ({name})")
         k_descale, v_descale = self._scales(layer)
+        if self._cascade_on and not (getattr(layer, "xai_temperature_len", -1) or 0) > 0:
+            # shared-prefix decode on the packed bytes: phase 1 cascade_mx4_kernel, phase 2 + merge rx_decode_attn_mx4
+            kb, vb, ksb, vsb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
+            self._cascade_call(q3, kb, vb, o3, layer.scaling, k_descale, v_descale, layer.logit_cap,
+                               sinks if sinks is None or sinks.dtype == torch.float32 else sinks.float(),
+                               page_size=self.page_size, k_scale_buffer=ksb, v_scale_buffer=vsb)
+            return o
         if self._is_mla_mx4_pool:  # one latent buffer: V is the first 512 columns of the same bytes
             kb, ksb = self.token_to_kv_pool.get_mx4_buffers(layer.layer_id)
             vb, vsb = kb, None

@@ -44,6 +44,7 @@ struct Options {
   int extend_mla = 1;         // the latent (576 / 512) extend kernel
   int extend_mla_shared_v = 1;  // V^T read from the K image when v aliases k[..., :512]
   int extend_mx4_native = -1; // backend: extends over a 4-bit pool through rx_extend_attn_mx4 (-1: by the shape rule of DESIGN 4.2c, 1 always, 0 never: gather + 16-bit extend)
+  int cascade_mx4 = 0;        // rx_extend_attn_mx4: 1 = the skip-extend, not-causal form on cascade_mx4_kernel (0, the default the measurement supports: extend_mx4_kernel, 0.89x its time)
   int decode_mla8_t64 = 0;    // ... in its 64-token-tile form (every wave owns 16 tokens of the tile; 0: the 32-token K-split form; A/B: DESIGN 4.1b)
   int merge_in_kernel_max_mb = 4;      // stage 2 inside the stage-1 kernel while the partials are at most this many MB ...
   int merge_in_kernel_max_mb_mla = 4;  // ... and for latent (576 / 512) rows

@@ -35,25 +35,6 @@
 
 namespace rx {
 
-struct Mx4ExtendArgs {
-  const uint16_t* q;
-  const uint16_t* k_ext;
-  const uint16_t* v_ext;
-  uint16_t* o;
-  int64_t q_stride_t, q_stride_h, k_stride_t, k_stride_h, v_stride_t, v_stride_h, o_stride_t, o_stride_h;
-  Mx4Pool k, v;
-  int32_t page_size;  // >= 1, or -(log2(page) + 1) for a power-of-two page (slot_offset)
-  const void* qo_indptr;
-  int32_t qo64;
-  const int32_t* kv_indptr;
-  const void* kv_indices;
-  float* lse;
-  int64_t lse_stride_t, lse_stride_h;
-  int32_t bs, hkv, group, mblocks;
-  float sm_scale, k_scale, v_scale, logit_cap;
-  int32_t causal, skip_extend;
-};
-
 constexpr int kMx4Tile = 64;  // tokens per staged tile = rows per workgroup
 
 template <typename T, int D, typename IdxT, bool LINEAR>
@@ -327,6 +308,8 @@ static void launch_extend_mx4(const Mx4ExtendArgs& a, bool idx64, bool linear, h
 #undef RX_EMX4
 }
 
+void launch_cascade_mx4(const Mx4ExtendArgs& a, int64_t max_rows, bool bf16, int d, bool idx64, bool linear, hipStream_t s);  // rx_cascade_mx4.hip
+
 }  // namespace rx
 
 using namespace rx;
@@ -421,6 +404,12 @@ static int extend_attn_mx4_impl(const rx_extend_params* p, const rx_kv_mx4_scale
                                   sc->k_page_stride == ps * sc->k_tok_stride && sc->v_page_stride == ps * sc->v_tok_stride);
   const bool idx64 = p->kv_indices_is_i64 != 0;
   auto s = static_cast<hipStream_t>(stream);
+  if (p->skip_extend && !p->is_causal && options().cascade_mx4) {
+    // the chunk-of-a-shared-prefix form (every row sees all of the prefix, many rows) on cascade_mx4_kernel, 128 rows per workgroup
+    // (opt-in: extend_mx4_kernel measured 0.89x its time on this form)
+    launch_cascade_mx4(a, static_cast<int64_t>(p->max_extend_len) * a.group, p->dtype == RX_BF16, dk, idx64, linear, s);
+    return check_launch("rx_extend_attn_mx4");
+  }
   if (p->dtype == RX_BF16) {
     if (dk == 64) launch_extend_mx4<BF16, 64>(a, idx64, linear, s);
     else launch_extend_mx4<BF16, 128>(a, idx64, linear, s);

@@ -157,6 +157,8 @@ struct Mx4DecodeArgs {
   const float* sinks;
   int32_t xai_len;
   const int32_t* order;
+  const int32_t* kv_start;  // req_to_token mode: request b attends tokens [kv_start[b], seq_len_b) only (or NULL)
+  int32_t all_partials;     // extra partials wait in stage 2: a request with ONE kv split writes a partial too
 };
 
 template <typename T, int D, typename IdxT, bool LINEAR>
@@ -186,20 +188,23 @@ __global__ __launch_bounds__(256, 2) void decode_mx4_kernel(const Mx4DecodeArgs 
   const int b = a.order ? a.order[bid % a.bs] : bid % a.bs;
   const int split = bid / a.bs;
 
-  int32_t seq_len;
+  int32_t seq_len, full_len;  // tokens this launch attends / the request's length
   const IdxT* idx;
   if (a.kv_indices) {
     const int32_t beg = a.kv_indptr[b];
-    seq_len = a.kv_indptr[b + 1] - beg;
+    seq_len = full_len = a.kv_indptr[b + 1] - beg;
     idx = reinterpret_cast<const IdxT*>(a.kv_indices) + beg;
   } else {  // IdxT == int32_t in this mode
-    seq_len = static_cast<int32_t>(load_idx(a.seq_lens, b, a.sl64));
-    idx = reinterpret_cast<const IdxT*>(a.req_to_token + load_idx(a.req_pool_indices, b, a.rpi64) * a.req_row_stride);
+    full_len = static_cast<int32_t>(load_idx(a.seq_lens, b, a.sl64));
+    const int32_t start = a.kv_start ? min(max(a.kv_start[b], 0), full_len) : 0;  // (attended_len, rx_decode.hip: stage 2 counts the same)
+    seq_len = full_len - start;
+    idx = reinterpret_cast<const IdxT*>(a.req_to_token + load_idx(a.req_pool_indices, b, a.rpi64) * a.req_row_stride) + start;
   }
   const int32_t splits = (a.num_kv_splits && a.max_kv_splits > 1) ? a.num_kv_splits[b] : 1;
   // a request with ONE kv split writes its final output here and stage 2 leaves it alone (direct_single, rx_decode.hip):
   // an empty request inside a split batch gets the zeros it gets from the 16-bit kernels
-  const bool single = a.max_kv_splits == 1 || splits == 1;
+  // (with extra partials every request's result is stage 2's: one split, or an empty suffix, leaves it the extras alone)
+  const bool single = a.max_kv_splits == 1 || (splits == 1 && !a.all_partials);
   const int gq = qb * 16 + r;  // q head inside the GQA group handled by this lane
   const bool q_valid = gq < a.group;
   const int h = kvh * a.group + gq;
@@ -230,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void decode_mx4_kernel(const Mx4DecodeArgs 
   float m_run = -INFINITY;  // running max (log2 domain), identical in the 4 lanes of a q head
   float l_run = 0.f;        // this lane's partial row sum
 
-  const float xai = xai_factor(a.xai_len, seq_len);
+  const float xai = xai_factor(a.xai_len, full_len);
   const float scale_log2 = a.sm_scale * kLog2e * xai;
 
   auto load_slots = [&](int t, int64_t& s0, int64_t& s1) {
@@ -602,8 +607,6 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
   RX_MX4_NO(p->k_new || p->v_new, "the fused store (k_new / v_new)");
   RX_MX4_NO(p->rope_cos_sin, "fused RoPE (rope_cos_sin)");
   RX_MX4_NO(p->score_bias, "score_bias");
-  RX_MX4_NO(p->kv_start, "kv_start");
-  RX_MX4_NO(p->num_extra_partials > 0, "extra partials (extra_o / extra_lse)");
   RX_MX4_NO(p->split_items, "split_items");
   RX_MX4_NO(p->unit_desc || p->unit_first_slots, "unit_desc / unit_first_slots");
   RX_MX4_NO(p->merge_counters, "merge_counters");
@@ -618,6 +621,20 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
                "rx_decode_attn_mx4: neither kv_indices nor req_to_token/req_pool_indices/seq_lens");
   }
   const int max_splits = (p->max_kv_splits < 1 || !p->num_kv_splits) ? 1 : p->max_kv_splits;
+  // shared-prefix (cascade) decode: the suffix [kv_start[b], seq_len_b) of the req_to_token rows, and the chunk partials of
+  // phase 1 (rx_extend_attn_mx4) merged by stage 2 -- every request writes its partials then, sinks join once, there
+  const int num_extra = p->num_extra_partials > 0 ? p->num_extra_partials : 0;
+  if (p->kv_start || num_extra) {
+    if (mla) return fail(RX_ERR_UNSUPPORTED, "rx_decode_attn_mx4: kv_start / extra partials are not supported on latent rows (576 / 512)");
+    if (p->kv_start && mode_a)
+      return fail(RX_ERR_UNSUPPORTED, "rx_decode_attn_mx4: kv_start applies to the req_to_token lookup only (with kv_indices, "
+                  "build the list with rx_build_kv_indices' kv_start)");
+    if (p->kv_start && p->xai_temperature_len > 0)
+      return fail(RX_ERR_UNSUPPORTED, "rx_decode_attn_mx4: xai_temperature_len with kv_start is not supported on a 4-bit pool");
+    if (num_extra)
+      RX_REQUIRE(p->extra_o && p->extra_lse && max_splits > 1,
+                 "rx_decode_attn_mx4: extra partials need extra_o, extra_lse and max_kv_splits > 1 (stage 2 merges them)");
+  }
   if (max_splits > 1)
     RX_REQUIRE(p->attn_logits && p->attn_lse, "rx_decode_attn_mx4: max_kv_splits=%d needs attn_logits and attn_lse", max_splits);
   // one (D / 8)-byte load per lane and row, D / 64 scale bytes beside it; 16-byte q loads
@@ -667,6 +684,8 @@ static int decode_attn_mx4_impl(const rx_decode_params* p, const rx_kv_mx4_scale
   a.sinks = p->sinks;
   a.xai_len = p->xai_temperature_len;
   a.order = p->request_order;
+  a.kv_start = p->kv_start;
+  a.all_partials = num_extra > 0;
   const int ps = p->kv.page_size;
   const bool linear = ps == 1 || (p->kv.k_page_stride == ps * p->kv.k_tok_stride && p->kv.v_page_stride == ps * p->kv.v_tok_stride &&
                                   sc->k_page_stride == ps * sc->k_tok_stride && sc->v_page_stride == ps * sc->v_tok_stride);

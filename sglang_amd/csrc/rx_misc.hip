@@ -129,7 +129,7 @@ static const OptionEntry kOptionTable[] = {
     {"extend_mla", &Options::extend_mla},                 {"extend_mla_shared_v", &Options::extend_mla_shared_v},
     {"decode_mla8_dma", &Options::decode_mla8_dma},       {"decode_mla8_t64", &Options::decode_mla8_t64},
     {"merge_in_kernel_max_mb", &Options::merge_in_kernel_max_mb}, {"merge_in_kernel_max_mb_mla", &Options::merge_in_kernel_max_mb_mla},
-    {"extend_mx4_native", &Options::extend_mx4_native},
+    {"extend_mx4_native", &Options::extend_mx4_native},   {"cascade_mx4", &Options::cascade_mx4},
 };
 static Options load_options() {  // once, at first use: RX_OPT_<NAME> (upper case) overrides a default
   Options o;

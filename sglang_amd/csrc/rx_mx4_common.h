@@ -43,4 +43,24 @@ inline Mx4Pool mx4_pool(const void* data, const void* scales, int64_t dps, int64
   return p;
 }
 
+// rx_extend_attn_mx4's launch arguments: extend_mx4_kernel (rx_extend_mx4.hip) and cascade_mx4_kernel (rx_cascade_mx4.hip)
+struct Mx4ExtendArgs {
+  const uint16_t* q;
+  const uint16_t* k_ext;
+  const uint16_t* v_ext;
+  uint16_t* o;
+  int64_t q_stride_t, q_stride_h, k_stride_t, k_stride_h, v_stride_t, v_stride_h, o_stride_t, o_stride_h;
+  Mx4Pool k, v;
+  int32_t page_size;  // >= 1, or -(log2(page) + 1) for a power-of-two page (slot_offset)
+  const void* qo_indptr;
+  int32_t qo64;
+  const int32_t* kv_indptr;
+  const void* kv_indices;
+  float* lse;
+  int64_t lse_stride_t, lse_stride_h;
+  int32_t bs, hkv, group, mblocks;
+  float sm_scale, k_scale, v_scale, logit_cap;
+  int32_t causal, skip_extend;
+};
+
 }  // namespace rx

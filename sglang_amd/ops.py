@@ -1125,6 +1125,25 @@ def shared_prefix_plan(req_to_token, req_pool_indices, seq_lens, plan, chunk_ind
     _L.check(st, "rx_shared_prefix_plan")
 
 
+def _check_mx4_call(who: str, mx4: bool, k_scale_buffer, v_scale_buffer, kv_layout, k_new, v_new) -> None:
+    """The cascade classes' 4-bit route: an object built with mx4=True takes both scale buffers and nothing the packed pool
+    cannot serve; any other object takes neither."""
+    given = k_scale_buffer is not None or v_scale_buffer is not None
+    if given != mx4 or (mx4 and (k_scale_buffer is None or v_scale_buffer is None)):
+        raise ValueError(f"{who}: k_scale_buffer and v_scale_buffer are given together, to an object built with mx4=True only")
+    if mx4:
+        _mx4_reject(kv_layout=kv_layout, k_new=k_new, v_new=v_new)
+
+
+def _mx4_cascade_layout(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size: int, hkv: int, d: int):
+    """(layout, scales) of the packed buffers a cascade object was built for: Hkv heads of D = 128 / 64 rows."""
+    _require_cuda(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer)
+    lay, sc, phkv, dk, dv, _ = _mx4_pool_args(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size)
+    if (phkv, dk, dv) != (hkv, d, d) or d not in (64, 128):
+        raise ValueError(f"4-bit pool rows hold {phkv} kv heads of {dk} / {dv} elements, the cascade object {hkv} of {d} (128 / 64)")
+    return lay, sc
+
+
 class CascadeDecode:
     """Shared-prefix (cascade) decode attention for one batch geometry (the reference only has the
     merge building block, kernels/ops/attention/merge_state.py:8-96).
@@ -1139,12 +1158,21 @@ class CascadeDecode:
       kernel over the suffixes ``[L, seq_len_b)``; its stage 2 merges the chunk partials with the kv splits.
 
     The result equals plain decode attention up to the partials' 16-bit rounding.  Not available with
-    sliding windows or the Grok temperature (position dependent per request)."""
+    sliding windows or the Grok temperature (position dependent per request).
+
+    ``mx4=True``: the object serves a 4-bit (MXFP4 block-16) pool at D 128 / 64 -- ``__call__`` then takes the packed data
+    buffers with ``k_scale_buffer`` / ``v_scale_buffer``; phase 1 is rx_extend_attn_mx4's skip-extend, not-causal form
+    (extend_mx4_kernel; rx::cascade_mx4_kernel with option ``cascade_mx4`` = 1, DESIGN 4.1c), phase 2 rx_decode_attn_mx4
+    with kv_start and the chunk partials, merged by the same stage 2."""
 
     def __init__(self, max_bs: int, num_q_heads: int, num_kv_heads: int, head_dim: int, dtype, device,
                  max_shared: int, cu_count: int = 256, min_shared: int = 1024, max_kv_splits: int = 16,
-                 num_chunks: Optional[int] = None, overlap: bool = False, v_head_dim: Optional[int] = None):
+                 num_chunks: Optional[int] = None, overlap: bool = False, v_head_dim: Optional[int] = None,
+                 mx4: bool = False):
         v_head_dim = head_dim if v_head_dim is None else int(v_head_dim)
+        self.mx4 = bool(mx4)
+        if self.mx4 and (head_dim not in (64, 128) or v_head_dim != head_dim or overlap):
+            raise ValueError("CascadeDecode(mx4=True): head_dim 64 / 128 (cascade_mx4_kernel / decode_mx4_kernel), no overlap")
         self.mla = (head_dim, v_head_dim) == (576, 512) and num_kv_heads == 1   # latent rows: rx::extend_mla_kernel
         if not self.mla and (head_dim not in (64, 96, 128, 256) or v_head_dim != head_dim):
             raise ValueError("CascadeDecode: head_dim 64 / 96 / 128 / 256, or the latent MLA shape 576 / 512 over one kv head "
@@ -1191,6 +1219,8 @@ class CascadeDecode:
             return self._fixed_chunks
         if self.mla:  # rows are (query, head) pairs there: ceil(bs * Hq / 128) workgroups per chunk
             return max(1, min(16, -(-self.cu_count // -(-bs * self.hq // 128))))
+        if self.mx4:  # rows are (query, q head of the group) pairs per kv head: ceil(bs * G / 128) * Hkv workgroups per chunk
+            return max(1, min(16, -(-self.cu_count // (-(-bs * (self.hq // self.hkv) // 128) * self.hkv))))
         return max(1, min(16, -(-self.cu_count // (-(-bs // 128) * self.hq))))
 
     def plan(self, req_to_token, req_pool_indices, seq_lens) -> None:
@@ -1208,7 +1238,7 @@ class CascadeDecode:
         # itself): the decode kernel's single-pass epilogue folds the chunk partials in -- no fp32 partials, no
         # stage-2 launch.  (The side-stream overlap joins before stage 2, so it keeps >= 2 slots.)
         self.max_kv_splits = native_max_kv_splits(bs, self.hq, self.hkv, self.cu_count, self.split_cap)
-        if self._side is not None or self.mla:  # (the MLA decode kernel has no single-pass fold: stage 2 merges)
+        if self._side is not None or self.mla or self.mx4:  # (the MLA / 4-bit decode kernels have no single-pass fold: stage 2 merges)
             self.max_kv_splits = max(2, self.max_kv_splits)
         if self.max_kv_splits > 1:
             get_num_kv_splits_native(self.num_kv_splits[:bs], self.suffix_lens[:bs], self.hq, self.hkv,
@@ -1223,10 +1253,12 @@ class CascadeDecode:
         return int(self.plan_buf[0].item())
 
     def __call__(self, q, k_buffer, v_buffer, o, sm_scale, k_scale=1.0, v_scale=1.0, logit_cap=0.0, sinks=None,
-                 page_size: int = 1, kv_layout=None, k_new=None, v_new=None) -> None:
+                 page_size: int = 1, kv_layout=None, k_new=None, v_new=None, k_scale_buffer=None, v_scale_buffer=None) -> None:
         """k_new / v_new: the step's KV store rides in the suffix launch (rx_decode_params.k_new): the newest token of
-        every request is the last of its suffix."""
+        every request is the last of its suffix.  k_scale_buffer / v_scale_buffer (an ``mx4=True`` object): k_buffer /
+        v_buffer are a 4-bit pool's packed data buffers (NHD or 4-D HND); no fused store there."""
         bs, S = self.bs, self.num_chunks
+        _check_mx4_call("CascadeDecode", self.mx4, k_scale_buffer, v_scale_buffer, kv_layout, k_new, v_new)
         if q.shape != (bs, self.hq, self.d):
             raise ValueError(f"CascadeDecode: q {tuple(q.shape)} != {(bs, self.hq, self.d)}")
         req_to_token, req_pool_indices, seq_lens = self._tabs
@@ -1247,6 +1279,9 @@ class CascadeDecode:
         if ent is None:
             if len(self._params) > 4096:
                 self._params.clear()
+            sc = None
+            if self.mx4:
+                kv_layout, sc = _mx4_cascade_layout(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size, self.hkv, self.d)
             pe = _extend_params(qf, qf, qf[..., : self.dv], of, k_buffer, v_buffer, self.qo_indptr, self.chunk_indptr,
                                 self.shared_indices, None, False, None, bs, k_scale, 1.0, sm_scale=sm_scale,
                                 logit_cap=logit_cap, lse_extend=lse_parts.view(S * bs, self.hq), skip_extend=True,
@@ -1256,8 +1291,10 @@ class CascadeDecode:
                                       self.max_kv_splits, sm_scale, k_scale,
                                       v_scale, logit_cap, None, page_size, kv_layout, kv_start=self.kv_start[:bs],
                                       extra_o=o_parts, extra_lse=lse_parts)
-            ent = self._params[key] = (pe, C.byref(pe), pd, C.byref(pd), (k_buffer, v_buffer, req_to_token))
-        pe, pe_ref, pd, pd_ref, _ = ent
+            ent = self._params[key] = (pe, C.byref(pe), pd, C.byref(pd),
+                                       (k_buffer, v_buffer, req_to_token, k_scale_buffer, v_scale_buffer, sc))
+        pe, pe_ref, pd, pd_ref, keep = ent
+        sc_ref = C.byref(keep[5]) if self.mx4 else None
         # per-forward tensors of the caller (fresh every step in eager serving): patched, not part of the key
         pd.req_pool_indices, pd.req_pool_indices_is_i64 = req_pool_indices.data_ptr(), _is64(req_pool_indices, "req_pool_indices")
         pd.seq_lens, pd.seq_lens_is_i64 = seq_lens.data_ptr(), _is64(seq_lens, "seq_lens")
@@ -1274,15 +1311,15 @@ class CascadeDecode:
 
         def phase1():
             q_rep.copy_(q.unsqueeze(0).expand(S, -1, -1, -1))
-            st = lib.rx_extend_attn(pe_ref, _stream(q))
+            st = lib.rx_extend_attn_mx4(pe_ref, sc_ref, _stream(q)) if self.mx4 else lib.rx_extend_attn(pe_ref, _stream(q))
             if st:
-                _L.check(st, "rx_extend_attn")
+                _L.check(st, "rx_extend_attn_mx4" if self.mx4 else "rx_extend_attn")
 
         def phase2(stages):  # suffixes [L, seq_len_b); stage 2 merges everything (sinks join once, there)
             pd.stages = stages
-            st = lib.rx_decode_attn(pd_ref, _stream(q))
+            st = lib.rx_decode_attn_mx4(pd_ref, sc_ref, _stream(q)) if self.mx4 else lib.rx_decode_attn(pd_ref, _stream(q))
             if st:
-                _L.check(st, "rx_decode_attn")
+                _L.check(st, "rx_decode_attn_mx4" if self.mx4 else "rx_decode_attn")
 
         if self._side is None:
             phase1()
@@ -1315,9 +1352,13 @@ class CascadeGroups:
 
     def __init__(self, max_bs: int, num_q_heads: int, num_kv_heads: int, head_dim: int, dtype, device,
                  max_shared_total: int, cu_count: int = 256, max_groups: int = 32, max_chunks: int = 16,
-                 max_kv_splits: int = 16):
+                 max_kv_splits: int = 16, mx4: bool = False):
         if head_dim not in (64, 96, 128, 256):
             raise ValueError("CascadeGroups: head_dim 64 / 96 / 128 / 256 (the MFMA extend and decode kernels)")
+        self.mx4 = bool(mx4)   # a 4-bit pool's packed buffers (D 128 / 64), as CascadeDecode(mx4=True)
+        if self.mx4 and head_dim not in (64, 128):
+            raise ValueError("CascadeGroups(mx4=True): head_dim 64 / 128 (cascade_mx4_kernel / decode_mx4_kernel)")
+        self._mx4_hkv = num_kv_heads if self.mx4 else 0
         self.max_bs, self.hq, self.hkv, self.d = int(max_bs), num_q_heads, num_kv_heads, head_dim
         self.cu_count, self.max_groups, self.max_chunks = int(cu_count), int(max_groups), int(max_chunks)
         self.split_cap = max(2, int(max_kv_splits))
@@ -1337,7 +1378,7 @@ class CascadeGroups:
         # rows of the gathered queries / chunk partials: C * M with C = layout()'s chunk count, which shrinks as the member
         # count M grows (C <= ceil(CUs / (ceil(M / 128) * Hq))) -- the maximum over reachable layouts, not
         # max_chunks * max_bs (16x oversized, ~1 GB at a 4096-request pool)
-        rows = self.rows_max = self.rows_bound(self.max_bs, num_q_heads, self.cu_count, self.max_chunks)
+        rows = self.rows_max = self.rows_bound(self.max_bs, num_q_heads, self.cu_count, self.max_chunks, self._mx4_hkv)
         self.q_rep = torch.zeros(rows * num_q_heads * head_dim, dtype=dtype, device=device)
         self.o_parts = torch.zeros(rows * num_q_heads * head_dim, dtype=dtype, device=device)
         self.lse_parts = torch.zeros(rows * num_q_heads, dtype=torch.float32, device=device)
@@ -1349,13 +1390,17 @@ class CascadeGroups:
         self.bs = self.members = self.num_chunks = self.num_groups = 0
 
     @staticmethod
-    def rows_bound(max_bs: int, hq: int, cu_count: int, max_chunks: int) -> int:
+    def rows_bound(max_bs: int, hq: int, cu_count: int, max_chunks: int, mx4_hkv: int = 0) -> int:
         """max over member counts M <= max_bs of layout()'s C * M: C <= min(max_chunks, ceil(CUs / (ceil(M/128) * Hq)))
-        (layout's workgroup count sum(ceil(size_g / 128)) * Hq is at least ceil(M / 128) * Hq)."""
+        (layout's workgroup count sum(ceil(size_g / 128)) * Hq is at least ceil(M / 128) * Hq).  mx4_hkv = Hkv of a 4-bit
+        pool: its phase-1 workgroups hold 128 (member, q head) rows of one kv head, at least ceil(M * G / 128) * Hkv."""
+        if mx4_hkv:
+            g = hq // mx4_hkv
+            return max(min(max_chunks, max(1, -(-cu_count // (-(-m * g // 128) * mx4_hkv)))) * m for m in range(1, max_bs + 1))
         return max(min(max_chunks, max(1, -(-cu_count // (-(-m // 128) * hq)))) * m for m in range(1, max_bs + 1))
 
     @staticmethod
-    def layout(groups, bs: int, hq: int, cu_count: int, max_chunks: int, chunk_align: int = 64):
+    def layout(groups, bs: int, hq: int, cu_count: int, max_chunks: int, chunk_align: int = 64, mx4_hkv: int = 0):
         """Host half of the plan (pure numpy, no device): returns a dict of int32 arrays -- the pseudo-request tables
         of phase 1 and the per-request tables of phase 2.  Pseudo-request p = c * G + g; the shared slot list is laid
         out in the same order, so both indptr arrays are monotone."""
@@ -1367,6 +1412,8 @@ class CascadeGroups:
             raise ValueError("CascadeGroups: groups must be disjoint sets of batch rows")
         M = int(sizes.sum())
         wgs = int((-(-sizes // 128)).sum()) * hq  # phase-1 workgroups per chunk
+        if mx4_hkv:  # a 4-bit pool: 128 (member, q head) rows of one kv head per workgroup
+            wgs = int((-(-sizes * (hq // mx4_hkv) // 128)).sum()) * mx4_hkv
         C = int(max(1, min(max_chunks, -(-cu_count // max(1, wgs)))))
         per = -(-(-(-lens // C)) // chunk_align) * chunk_align          # chunk length of each group, aligned
         starts = np.concatenate([[0], np.cumsum(sizes)])[:-1]
@@ -1396,7 +1443,7 @@ class CascadeGroups:
         bs = self.bs = req_pool_indices.shape[0]
         if bs > self.max_bs or len(groups) > self.max_groups:
             raise ValueError(f"CascadeGroups: bs {bs} / {len(groups)} groups beyond max_bs {self.max_bs} / max_groups {self.max_groups}")
-        lay = self.layout(groups, bs, self.hq, self.cu_count, self.max_chunks)
+        lay = self.layout(groups, bs, self.hq, self.cu_count, self.max_chunks, mx4_hkv=self._mx4_hkv)
         C, G, M = lay["C"], lay["G"], lay["M"]
         if lay["total_shared"] > self.max_shared_total:
             raise ValueError(f"CascadeGroups: {lay['total_shared']} shared tokens > max_shared_total {self.max_shared_total}")
@@ -1426,13 +1473,20 @@ class CascadeGroups:
             self.shared_indices[:T] = req_to_token[row, col]
         torch.sub(seq_lens.to(torch.int32), self.kv_start, out=self.suffix_lens[:bs])
         self.max_kv_splits = native_max_kv_splits(bs, self.hq, self.hkv, self.cu_count, self.split_cap)
+        if self.mx4:  # (the 4-bit decode kernel has no single-pass fold: stage 2 merges the extras)
+            self.max_kv_splits = max(2, self.max_kv_splits)
         if self.max_kv_splits > 1:
             get_num_kv_splits_native(self.num_kv_splits[:bs], self.suffix_lens[:bs], self.hq, self.hkv,
                                      self.max_kv_splits, self.cu_count)
 
     def __call__(self, q, k_buffer, v_buffer, o, sm_scale, k_scale=1.0, v_scale=1.0, logit_cap=0.0, sinks=None,
-                 page_size: int = 1, kv_layout=None, k_new=None, v_new=None) -> None:
+                 page_size: int = 1, kv_layout=None, k_new=None, v_new=None, k_scale_buffer=None, v_scale_buffer=None) -> None:
+        """k_scale_buffer / v_scale_buffer (an ``mx4=True`` object): k_buffer / v_buffer are a 4-bit pool's packed data."""
         bs, nc, M = self.bs, self.num_chunks, self.members
+        _check_mx4_call("CascadeGroups", self.mx4, k_scale_buffer, v_scale_buffer, kv_layout, k_new, v_new)
+        sc = None
+        if self.mx4:
+            kv_layout, sc = _mx4_cascade_layout(k_buffer, v_buffer, k_scale_buffer, v_scale_buffer, page_size, self.hkv, self.d)
         if q.shape != (bs, self.hq, self.d):
             raise ValueError(f"CascadeGroups: q {tuple(q.shape)} != {(bs, self.hq, self.d)}")
         req_to_token, req_pool_indices, seq_lens = self._tabs
@@ -1450,7 +1504,10 @@ class CascadeGroups:
                                 self.shared_indices, None, False, None, self.max_group, k_scale, 1.0, sm_scale=sm_scale,
                                 logit_cap=logit_cap, lse_extend=lse_parts, skip_extend=True, page_size=page_size,
                                 kv_layout=kv_layout, _num_kv_heads=self.hkv, avg_kv_len_hint=0)
-            _L.check(self._lib.rx_extend_attn(C.byref(pe), _stream(q)), "rx_extend_attn")
+            if self.mx4:
+                _L.check(self._lib.rx_extend_attn_mx4(C.byref(pe), C.byref(sc), _stream(q)), "rx_extend_attn_mx4")
+            else:
+                _L.check(self._lib.rx_extend_attn(C.byref(pe), _stream(q)), "rx_extend_attn")
             extra_o = o_parts.view(nc, M, self.hq, self.d)
             extra_lse = lse_parts.view(nc, M, self.hq)
         pd = _decode_paged_params(q, k_buffer, v_buffer, o, req_to_token, req_pool_indices, seq_lens, attn_logits, attn_lse,
@@ -1458,6 +1515,8 @@ class CascadeGroups:
                                   sinks, page_size, kv_layout, kv_start=self.kv_start, extra_o=extra_o,
                                   extra_lse=extra_lse, extra_index=self.extra_index if M else None)
         _set_new_kv(pd, k_new, v_new, bs)
+        if self.mx4:
+            return _L.check(self._lib.rx_decode_attn_mx4(C.byref(pd), C.byref(sc), _stream(q)), "rx_decode_attn_mx4")
         _L.check(self._lib.rx_decode_attn(C.byref(pd), _stream(q)), "rx_decode_attn")
 
 
